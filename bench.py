@@ -6,17 +6,22 @@ on the configuration named by --config (default C3 = BASELINE.json configs[2], t
 target config: 1920x1080, 8 spheres + 1 plane, 2 lights, recursive mirror reflections depth 4),
 with the scene resident in HBM and the frame written to HBM.
 
+A plain run does what its headline figure needs: it sets up, warms up, times --steps frames, writes
+the last timed frame when --dump-outputs DIR is given, and prints the line.  Everything named "--full"
+below is measured only with --full (off by default): further configs, the Tick() rates, the work
+count, the per-launch event pass, the CPU baseline, and at N > 1 the frame check and plugin_tick.
+
 N = 1: the timed frames run as balanced launches of up to 64 frames (rt_render_bands_batch),
 one launch in flight, back to back on one stream: HIP events around the timed region / launches
-give roofline.kernel_avg_ms (which rocprofv3's kernel trace of the same command reproduces); an
-untimed second pass times each launch with its own event pair (kernel_avg_ms_launch_events).  C2 (configs[1]: depth 1,
+give roofline.kernel_avg_ms (which rocprofv3's kernel trace of the same command reproduces); --full: an
+untimed second pass times each launch with its own event pair (kernel_avg_ms_launch_events), C2 (configs[1]: depth 1,
 1 light), C4 and C5 are measured in the same run ("also"), and the plugin path's Tick() (rt_render / rt_render_async
 into registered host memory, PCIe included) for C2-C5 under tick_by_config.
 
 N > 1 (`--gpus N`: one process per GPU; started here through torch.distributed.run when no
 launcher set WORLD_SIZE): the frame is split into interleaved 8-row bands, band b on rank
 b % N, and the band sets are gathered to rank 0 over RCCL (torch.distributed backend "nccl"
-is RCCL on ROCm) -- strong scaling of a fixed frame.  Then rank 0 runs the plugin path's own multi-GPU
+is RCCL on ROCm) -- strong scaling of a fixed frame.  With --full rank 0 then runs the plugin path's own multi-GPU
 Tick() in one process (Context(N): every device hands its bands to the host frame over its own PCIe
 link), reported under plugin_tick.
 
@@ -121,7 +126,7 @@ def parse(argv=None):
     ap.add_argument("--dist-path", action="store_true",
                     help="rehearsal: run the N>1 band/gather path even with one process (RCCL world of 1)")
     ap.add_argument("--no-verify", dest="verify", action="store_false",
-                    help="N>1 path: skip the check after the timed run (default: rank 0 compares every frame still "
+                    help="N>1 path, --full: skip the check after the timed run (default: rank 0 compares every frame still "
                          "in its frame rings -- tiles: all frames of a run of <= 3 batches -- with a single-launch "
                          "render of the same view, reports verified_frames, and every rank exits 3 on a mismatch)")
     ap.add_argument("--verify", dest="verify", action="store_true", help="(the default; kept for old command lines)")
@@ -140,7 +145,35 @@ def parse(argv=None):
                          "the run then has the bench's launch shape)")
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                     help="rocprofv3 PMC summary (HBM bytes per trace launch) for roofline.traffic")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure too: the untimed per-launch-event pass, the work count, "
+                         "the Tick() rates, the --also / --also-dist / --tick-configs configs, the CPU baseline and (N > 1) "
+                         "the frame check and the plugin path's multi-GPU Tick().  Without it a run sets up, warms up, "
+                         "times --steps frames of --config, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the frame the last timed step produced (rank 0's at N > 1) to "
+                         "DIR/frame_rgb.npy: float32 (rows, W, 3), R G B in 0..255, and the frame rows it holds to "
+                         "DIR/frame_rows.npy (all of them, or a fixed seeded sample when the frame exceeds 48 MB)")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run measures the headline figure alone
+        args.also = args.also_dist = args.tick_configs = ""
+        args.no_tick = args.no_cpu_baseline = True
+        args.verify = False
+    return args
+
+
+def dump_frame(out_dir, pixels, W, H, limit=48 << 20):
+    """--dump-outputs: one frame (W*H int32 pixels, 0x00RRGGBB, on any device) as float32 R G B planes
+    per pixel.  A frame above `limit` bytes keeps a sample of whole rows, the same rows in every run."""
+    import numpy as np
+    px = pixels.detach().cpu().numpy().reshape(H, W)
+    rows = np.arange(H)
+    if H * W * 12 > limit:
+        rows = np.sort(np.random.default_rng(0).choice(H, size=max(1, limit // (W * 12)), replace=False))
+    rgb = np.stack([(px[rows] >> s) & 0xFF for s in (16, 8, 0)], axis=-1).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame_rgb.npy"), rgb)
+    np.save(os.path.join(out_dir, "frame_rows.npy"), rows.astype(np.float64))
 
 
 def launch_command(argv, n, port):
@@ -290,7 +323,7 @@ def plan_launches(n, fpl):
     return [base + 1] * extra + [base] * (k - extra)
 
 
-def measure_single(ctx, sc, args, torch, abi, steps, warmup):
+def measure_single(ctx, sc, args, torch, abi, steps, warmup, dump=False):
     """N = 1: `steps` frames of `sc` in balanced launches of <= --frames-per-launch frames
     (rt_render_bands_batch: one launch, grid z = frame, every frame traced in full into its own
     slot), --inflight launches in flight.  Timed between two torch.cuda.synchronize() calls."""
@@ -302,6 +335,7 @@ def measure_single(ctx, sc, args, torch, abi, steps, warmup):
     stream = torch.cuda.current_stream()
     streams = [stream] + [torch.cuda.Stream() for _ in range(nf - 1)]
     k = [0]
+    last = [0, 1]  # the latest launch: its buffer and its frames
 
     def issue(n, lim=fpl):
         for m in plan_launches(n, min(lim, cap)):
@@ -309,6 +343,7 @@ def measure_single(ctx, sc, args, torch, abi, steps, warmup):
                 raise RuntimeError(f"launch of {m} frames exceeds the {cap}-frame buffer")
             i = k[0] % nf
             k[0] += 1
+            last[:] = [i, m]
             ctx.render_bands_batch(W, H, H, 0, 1, m, bufs[i].data_ptr(), W * H * 4, abi.RT_BANDS_INT32,
                                    streams[i].cuda_stream)
 
@@ -345,8 +380,10 @@ def measure_single(ctx, sc, args, torch, abi, steps, warmup):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     st = ctx.stats()
+    # what the last timed step left in its slot of the last launch (--dump-outputs), before anything runs again
+    last_frame = bufs[last[0]][(last[1] - 1) * W * H:last[1] * W * H].clone() if dump else None
     launch_s = None
-    if nf == 1:  # cross-check (untimed): the same launches, an event pair around each
+    if nf == 1 and args.full:  # cross-check (untimed): the same launches, an event pair around each
         ctx.set_timing(1)
         ctx.reset_stats()
         issue(steps)
@@ -356,7 +393,7 @@ def measure_single(ctx, sc, args, torch, abi, steps, warmup):
     ctx.set_timing(64)  # the library's default sampling
     return {"elapsed": elapsed, "period_s": ev0.elapsed_time(ev1) / 1e3 / steps, "stats": st, "host_s": host_s,
             "launches": len(plan_launches(steps, fpl)), "warmup_effective": done, "inflight": nf,
-            "launch_events_s": launch_s}
+            "launch_events_s": launch_s, "last_frame": last_frame}
 
 
 def single_summary(sc, m, steps):
@@ -568,7 +605,8 @@ def main():
         dist.init_process_group("gloo", rank=rank, world_size=world)
     else:
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local))
-    out = dist_leg(args, args.config, rank, world, local, torch, dist, Context, abi, scenes, size=args.size)
+    out = dist_leg(args, args.config, rank, world, local, torch, dist, Context, abi, scenes, size=args.size,
+                   dump=args.dump_outputs)
     # further configs through the same pipeline (default C5: 7680x4320, the configuration BASELINE
     # names for the 1/2/4/8-GPU scaling curve), each with its own value / ms_per_step / n_gpus
     also = [c for c in (x.strip() for x in args.also_dist.split(",")) if c and c.upper() != args.config.upper()]
@@ -706,9 +744,10 @@ def rank0_tail_rows(ctx, W, H, band_rows, world, rank, torch, dist, log=None):
     return int(ans.item())
 
 
-def dist_leg(args, config_name, rank, world, local, torch, dist, Context, abi, scenes, size=""):
+def dist_leg(args, config_name, rank, world, local, torch, dist, Context, abi, scenes, size="", dump=""):
     """One N > 1 measurement of `config_name` through the band pipeline (rank 0 returns the
-    line's dict, the other ranks None).  Every rank runs every leg, so the collectives match."""
+    line's dict, the other ranks None).  Every rank runs every leg, so the collectives match.
+    dump: rank 0 writes the last timed step's assembled frame there (--dump-outputs)."""
     sc = scenes.config(config_name)
     if size:  # probe runs only (--size): the config's scene at another frame size
         w_, h_ = map(int, size.lower().split("x"))
@@ -991,19 +1030,29 @@ def dist_leg(args, config_name, rank, world, local, torch, dist, Context, abi, s
             print(f"[rank {rank}] verify: {sc.name} frames differ from a single-launch render", file=sys.stderr,
                   flush=True)
             sys.exit(3)
-    # Kernel duration per launch: an untimed second pass of the same frames (same collectives on
-    # every rank) with a HIP event pair around every launch on its own stream (rt_set_timing 1;
+    if dump and rank == 0:  # the last timed step's frame as rank 0 assembled it, before anything runs again
+        if tg is not None and tg.frames is not None:
+            last = tg.ring_of(tg.batch - 1).view(tg.F, W * H)[(args.steps - 1) % tg.F]
+        elif tg is None and frame is not None:
+            last = frame
+        else:
+            raise SystemExit("--dump-outputs: rank 0 holds no assembled frame on this path")
+        dump_frame(dump, last, W, H)
+    # Kernel duration per launch (--full): an untimed second pass of the same frames (same collectives
+    # on every rank) with a HIP event pair around every launch on its own stream (rt_set_timing 1;
     # what rocprofv3's kernel trace reports too).  The frame period -- HIP events around the timed
-    # region / steps -- is shorter when frames overlap.
-    ctx.set_timing(1)
-    ctx.reset_stats()
-    run(args.steps)
-    finish()
-    torch.cuda.synchronize()
-    st2 = ctx.stats()
+    # region / steps -- is shorter when frames overlap; a plain run reports it per launch instead.
+    kernel_s = period_s * launch_frames
+    if args.full:
+        ctx.set_timing(1)
+        ctx.reset_stats()
+        run(args.steps)
+        finish()
+        torch.cuda.synchronize()
+        st2 = ctx.stats()
+        sampled_s = st2["kernel_ms"] / 1e3 / max(1, st2["timed_launches"])
+        kernel_s = sampled_s if st2["timed_launches"] else period_s
     ctx.set_timing(64)  # the library's default sampling
-    sampled_s = st2["kernel_ms"] / 1e3 / max(1, st2["timed_launches"])
-    kernel_s = sampled_s if st2["timed_launches"] else period_s
     if distributed:
         t = torch.tensor([elapsed, float(rays), float(f_alg), kernel_s], dtype=torch.float64, device="cuda")
         tmax = t.clone()
@@ -1069,8 +1118,9 @@ def dist_leg(args, config_name, rank, world, local, torch, dist, Context, abi, s
                 "kernel": "trace_direct_kernel" if sc and len(sc.spheres) < 12 else "trace_bundle_kernel",
                 "kernel_avg_ms": kernel_s * 1e3,
                 "frames_per_launch": launch_frames,
-                "kernel_avg_source": "an untimed second pass of the same run with a HIP event pair around every "
-                                     "launch on its stream (rt_set_timing 1), max over ranks",
+                "kernel_avg_source": ("an untimed second pass of the same run with a HIP event pair around every "
+                                      "launch on its stream (rt_set_timing 1), max over ranks") if args.full
+                else "frame period x frames per launch, max over ranks (--full: a per-launch event pass)",
                 "frame_period_ms": period_s * 1e3,
                 "note": "algorithmic bytes = 4 B framebuffer store per pixel x pixels per launch; the path is "
                         "FP32-VALU-bound",
@@ -1179,7 +1229,9 @@ def main_single(args, torch, Context, abi, scenes):
     steps = args.steps
     ctx = Context(1)
     ctx.set_scene(sc)
-    m = measure_single(ctx, sc, args, torch, abi, steps, args.warmup)
+    m = measure_single(ctx, sc, args, torch, abi, steps, args.warmup, dump=bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_frame(args.dump_outputs, m["last_frame"], W, H)
     r = single_summary(sc, m, steps)
     pmc = load_pmc(args.pmc, sc.name, 1)
     # PMC summaries are per dispatch of `frames_per_launch` frames (tools/pmc.sh): per frame here
@@ -1229,7 +1281,7 @@ def main_single(args, torch, Context, abi, scenes):
             "kernel_avg_source": ("HIP events around the timed region on the launch stream / launches (one launch "
                                   "in flight, launches back to back: the launches alone on the GPU, as rocprofv3's "
                                   "kernel trace of the same command); kernel_avg_ms_launch_events = an untimed "
-                                  "second pass of the same launches with an event pair around each")
+                                  "second pass of the same launches with an event pair around each (--full only)")
             if isolated else "sampled HIP event pairs of overlapping launches (--inflight > 1)",
             "note": "algorithmic bytes = 4 B framebuffer store per pixel x frames per launch; traffic = PMC "
                     "FETCH_SIZE x 2 + WRITE_SIZE per launch (profiles/pmc_traffic.json); the path is "

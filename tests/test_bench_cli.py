@@ -77,6 +77,39 @@ def test_cpu_baseline_reports_its_spread():
     assert out["cores"] >= 1 and "frame_ms_p10_p50_p90" in out["sample"]
 
 
+def test_plain_run_measures_the_headline_alone():
+    """Without --full every leg beside the timed steps is off, whatever its own option says; with it the
+    options mean what they say."""
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5", "--also", "C4", "--cpu-seconds", "5"])
+    assert not a.full and a.steps == 20 and a.warmup == 5 and a.dump_outputs == ""
+    assert a.also == a.also_dist == a.tick_configs == "" and a.no_tick and a.no_cpu_baseline and not a.verify
+    f = bench.parse(["--full"])
+    assert f.full and f.also == "C2,C4,C5" and f.also_dist == "C5" and f.tick_configs == "C2,C4,C5"
+    assert not f.no_tick and not f.no_cpu_baseline and f.verify
+    g = bench.parse(["--full", "--no-tick", "--no-verify", "--also", ""])
+    assert g.no_tick and not g.verify and g.also == "" and not g.no_cpu_baseline
+
+
+def test_dump_frame_channels_and_fixed_sample(tmp_path):
+    """--dump-outputs: 0x00RRGGBB pixels as float32 R G B per pixel with the rows they came from; a frame above
+    the size limit keeps the same sorted sample of whole rows in every run."""
+    import numpy as np
+    import torch
+    W, H = 7, 5
+    px = (np.arange(W * H, dtype=np.int64) * 0x03A7F1 % (1 << 24)).astype(np.int32)
+    bench.dump_frame(str(tmp_path / "a"), torch.from_numpy(px), W, H)
+    rgb, rows = np.load(tmp_path / "a" / "frame_rgb.npy"), np.load(tmp_path / "a" / "frame_rows.npy")
+    assert rgb.dtype == np.float32 and rgb.shape == (H, W, 3) and rows.dtype == np.float64
+    assert np.array_equal(rows, np.arange(H))
+    back = (rgb[..., 0].astype(np.int32) << 16) | (rgb[..., 1].astype(np.int32) << 8) | rgb[..., 2].astype(np.int32)
+    assert np.array_equal(back.ravel(), px)
+    for d in ("b", "c"):  # room for 2 of the 5 rows
+        bench.dump_frame(str(tmp_path / d), torch.from_numpy(px), W, H, limit=2 * W * 12)
+    rows_b, rows_c = np.load(tmp_path / "b" / "frame_rows.npy"), np.load(tmp_path / "c" / "frame_rows.npy")
+    assert rows_b.shape == (2,) and np.array_equal(rows_b, rows_c) and rows_b[0] < rows_b[1] < H
+    assert np.array_equal(np.load(tmp_path / "b" / "frame_rgb.npy"), rgb[rows_b.astype(int)])
+
+
 def test_percentiles_nearest_rank():
     assert bench.percentiles([5, 1, 2, 3, 4]) == [1, 3, 5]
     assert bench.percentiles([7]) == [7, 7, 7]

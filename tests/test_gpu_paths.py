@@ -65,6 +65,31 @@ def test_bench_launch_shape_every_frame_golden(gpu_ctx, golden, cid, steps, infl
         assert st[k] == steps * e["stats"][k], k  # frame 0 counts for every frame of a batch
 
 
+def test_plain_bench_dumps_its_last_timed_frame(tmp_path, golden):
+    """A plain bench.py run (no --full) of 70 frames -- two launches of 35: the dumped frame is the last slot of the
+    last launch -- writes the golden C3 frame as R G B planes, and its line carries the headline alone."""
+    import json
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "70", "--warmup", "3",
+           "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 70 and line["roofline"]["launches"] == 2 and line["ms_per_step"] > 0
+    assert line["unit"] == "Mray/s" and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert line["config"]["rays_per_frame"] == sum(golden["cases"]["C3"]["stats"][k] for k in
+                                                   ("primary_rays", "reflect_rays", "shadow_rays"))
+    for k in ("also", "tick_by_config", "work_per_frame", "tick_fps_incl_d2h"):
+        assert k not in line, k
+    assert line["cpu_baseline"] is None
+    rgb, rows = np.load(out / "frame_rgb.npy"), np.load(out / "frame_rows.npy")
+    assert rgb.dtype == np.float32 and rgb.shape == (1080, 1920, 3) and np.array_equal(rows, np.arange(1080))
+    px = (rgb[..., 0].astype(np.int32) << 16) | (rgb[..., 1].astype(np.int32) << 8) | rgb[..., 2].astype(np.int32)
+    assert crc(px) == golden["cases"]["C3"]["crc32"]
+
+
 def test_ppm_of_gpu_frame_matches_oracle(tmp_path, oracle):
     """Tick() of the verbatim reference scene (512x512, 2 lights, limit 32) on the GPU, written
     by rt_write_ppm: the RGB bytes are the oracle's pixels, byte for byte."""
@@ -130,8 +155,8 @@ def test_tile_pipeline_on_cuda_streams(extra, shape):
     size = {"small": ["--size", "640x360", "--steps", "40", "--warmup", "16", "--batch", "8"],
             "full": ["--steps", "300", "--warmup", "64"],
             "short": ["--steps", "20", "--warmup", "5"]}[shape]
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dist-path", "--config", "C2",
-           "--no-cpu-baseline"] + size + extra  # (frames verified by default on the N > 1 path)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dist-path", "--config", "C2",
+           "--no-cpu-baseline"] + size + extra  # (--full: frames verified by default on the N > 1 path)
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     import json
@@ -152,9 +177,9 @@ def test_bench_multi_rank_rehearsal(world, extra):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--rehearse-gloo",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--rehearse-gloo",
            "--master-port", str(_free_port()), "--config", "C3", "--size", "640x360", "--steps", "48", "--warmup", "16",
-           "--batch", "8", "--no-cpu-baseline"] + extra  # (frames verified by default at N > 1)
+           "--batch", "8", "--no-cpu-baseline"] + extra  # (--full: frames verified by default at N > 1)
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     import json
@@ -174,7 +199,7 @@ def test_driver_shape_forced_repeat_counts_one_attempt():
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
         env.pop("WORLD_SIZE", None)
         # (--rank0-codec: rank 0 ships its own bands through the codec, so the world-1 wire is not empty)
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dist-path", "--rank0-codec", "--config", "C2",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dist-path", "--rank0-codec", "--config", "C2",
                "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--also-dist", "", "--spec-margin", margin]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=110)
         assert r.returncode == 0, r.stderr[-2000:]

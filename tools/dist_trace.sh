@@ -5,8 +5,9 @@
 set -eo pipefail
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=${DIST_OUT:-dist_trace}
-mkdir -p $R/gpurun_out/$O
+D=$R/${OUT:-out}/$O
+mkdir -p $D
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --hip-runtime-trace --output-format csv -d $R/gpurun_out/$O/prof -o dist \
-    -- python3 -u $R/bench.py --dist-path ${DIST_FLAGS---rank0-codec} --steps 20 --warmup 5 --also-dist "" > $R/gpurun_out/$O/bench.txt 2>&1
-cd $R && python3 tools/dist_stages.py gpurun_out/$O/prof > gpurun_out/$O/stages.txt 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --hip-runtime-trace --output-format csv -d $D/prof -o dist \
+    -- python3 -u $R/bench.py --dist-path ${DIST_FLAGS---rank0-codec} --full --steps 20 --warmup 5 --also-dist "" > $D/bench.txt 2>&1
+cd $R && python3 tools/dist_stages.py $D/prof > $D/stages.txt 2>&1

@@ -19,6 +19,7 @@ for cfg in "$@"; do
     rm -rf "gpurun_out/trace_$cfg"
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "gpurun_out/trace_$cfg" -o run \
         -- python3 bench.py --config "$cfg" --also "" --no-cpu-baseline --no-tick --pmc gpurun_out/pmc_traffic.json \
+        --full \
         > "gpurun_out/trace_bench_$cfg.json" 2> "gpurun_out/trace_$cfg.log"
     rc=$?; echo "trace $cfg rc=$rc: $(tail -c 200 gpurun_out/trace_bench_$cfg.json)"; [ $rc -eq 0 ] || exit $rc
     find "gpurun_out/trace_$cfg" -name "*kernel_stats.csv" -exec cp {} "gpurun_out/trace_${cfg}_kernel_stats.csv" \;

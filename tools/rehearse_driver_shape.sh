@@ -10,7 +10,7 @@ for n in ${RANKS:-2 4 8}; do
     port=$((port + 1))
     log=gpurun_out/rehearse_driver_$n.log
     timeout -k 10 300 python bench.py --gpus $n --rehearse-gloo --master-port $port --steps 20 --warmup 5 \
-        --verify --no-cpu-baseline > $log 2>&1
+        --full --verify --no-cpu-baseline > $log 2>&1
     rc=$?
     echo "== N=$n rc=$rc: $(grep -h '^{' $log | tail -1 | python3 -c 'import sys,json; d=json.loads(sys.stdin.read() or "{}"); print(d.get("n_gpus"), "verified", d.get("verified_frames"), d.get("config",{}).get("parallelism","")[:140])' 2>/dev/null)"
     if [ $rc -ne 0 ]; then grep -v amdgpu.ids $log | tail -5; exit $rc; fi

@@ -11,7 +11,7 @@ for spec in "2 auto C2 --batch 16" "3 auto C3 --batch 8" "4 on C2 --batch 16" "4
     port=$((port + 1))
     log=gpurun_out/rehearse_${n}_${comp}_${cfg}.log
     timeout -k 10 240 python bench.py --gpus $n --rehearse-gloo --master-port $port --config $cfg --size 960x540 \
-        --steps 96 --warmup 32 --compositor $comp --verify --no-cpu-baseline "$@" > $log 2>&1
+        --steps 96 --warmup 32 --compositor $comp --full --verify --no-cpu-baseline "$@" > $log 2>&1
     rc=$?
     echo "== N=$n compositor=$comp $cfg $* rc=$rc: $(grep -h '^{' $log | tail -1 | python3 -c 'import sys,json; d=json.loads(sys.stdin.read() or "{}"); print(d.get("n_gpus"), d.get("verified_frames"), round(d.get("ms_per_step",0)*1e3,1), "us/frame", d.get("config",{}).get("parallelism","")[:90])' 2>/dev/null)"
     if [ $rc -ne 0 ]; then tail -5 $log; [ $rc -eq 124 ] || [ $rc -eq 137 ] && exit $rc; fi

@@ -15,8 +15,8 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 echo "gpu tests: $(tail -1 $O/gpu.log)"
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { cat $O/smoke.log; exit 1; }
 echo "smoke: $(tail -1 $O/smoke.log)"
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver.json 2> $O/driver.err || { tail $O/driver.err; exit 1; }
-timeout -k 10 500 python bench.py ${2:+--steps $2} > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/driver.json 2> $O/driver.err || { tail $O/driver.err; exit 1; }
+timeout -k 10 500 python bench.py --full ${2:+--steps $2} > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 for f in driver bench; do
 python3 - $O/$f.json $f <<'PY'
 import json, sys

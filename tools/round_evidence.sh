@@ -15,6 +15,6 @@ step() {
 echo "nproc=$(nproc) affinity=$(python3 -c 'import os;print(len(os.sched_getaffinity(0)))') cpu.max=$(cat /sys/fs/cgroup/cpu.max 2>/dev/null)"
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest_gpu 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread
-step bench_driver 300 python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 20
-step bench_default 300 python bench.py --no-cpu-baseline --also C3,C4,C5
+step bench_driver 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-seconds 20
+step bench_default 300 python bench.py --full --no-cpu-baseline --also C3,C4,C5
 bash tools/profile_round.sh ${CONFIGS:-C2 C3 C4 C5}
