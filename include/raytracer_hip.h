@@ -196,6 +196,24 @@ int rt_set_camera(rt_ctx* ctx, const rt_camera* camera);
  * the view's height) -- the multi-GPU pipeline's tracing ranks when rank 0 renders the frame's last rows
  * itself; 0 (the default) = each render's own height.  The debug view ignores it. */
 int rt_set_view_height(rt_ctx* ctx, int view_height);
+/* (ABI 10 addition) Supersampling: k = 1 (the default, off), 2, 4 or 8 samples per pixel and axis.  With
+ * k > 1 every render that writes pixels -- rt_render, rt_render_async (which captures the factor with the
+ * camera), rt_render_device, rt_render_bands, rt_render_bands_ex in every format and
+ * rt_render_bands_batch, on contexts of any n_gpus -- still produces a width x height output, and all
+ * arguments stay in output pixels (width, height, band_rows, band indices, buffer sizes, rt_set_view_height).
+ * Sample (i, j) of output pixel (x, y) is the reference's pixel (k x + i, k y + j) of a k width x k height
+ * frame (TracePixel :962-971), and the output pixel is, per 8-bit channel, the round-half-up mean of its
+ * k*k samples after ShiftColor: (sum + k*k/2) >> 2 log2 k.  The trace kernels reduce each block in
+ * registers: no sample buffer exists and the frame that leaves the device keeps its size.
+ * (long long) k width * k height must not exceed 2^31 - 1 (RT_ERR_INVALID_ARG from the render calls).
+ * Statistics: frames and pixels count output frames and pixels; primary_rays, reflect_rays, shadow_rays
+ * and the test counts count samples (the reference's counts at k width x k height).
+ * While k > 1, rt_render_bands_tiles and rt_count_work return RT_ERR_UNSUPPORTED; rt_debug_segments
+ * ignores the factor (as it ignores the view height).  Single frames at k > 1 run in natural tile order
+ * (rt_dispatch_order's tuner serves k = 1 only).  k = 1 is exactly the library without this call.
+ * Returns RT_ERR_INVALID_ARG for a NULL ctx or any other k. */
+int rt_set_supersampling(rt_ctx* ctx, int k);
+int rt_get_supersampling(const rt_ctx* ctx, int* out_k);
 int rt_get_camera(const rt_ctx* ctx, rt_camera* camera);
 int rt_camera_view(const rt_camera* camera, int width, int height, rt_view* out_view);
 int rt_camera_on_key(rt_camera* camera, int key);

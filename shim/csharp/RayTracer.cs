@@ -46,6 +46,7 @@ internal static class Native {
     [DllImport(Lib)] internal static extern int rt_set_timing(IntPtr ctx, int every);
     [DllImport(Lib)] internal static extern int rt_dispatch_order(IntPtr ctx, out int order);
     [DllImport(Lib)] internal static extern int rt_set_counting(IntPtr ctx, int on);  // ABI 10
+    [DllImport(Lib)] internal static extern int rt_set_supersampling(IntPtr ctx, int k);  // ABI 10 addition
 
     internal static void Check(int rc, IntPtr ctx) {
         if (rc != 0) throw new InvalidOperationException($"libraytracer_hip error {rc}: {Marshal.PtrToStringAnsi(rt_last_error(ctx))}");
@@ -69,6 +70,9 @@ internal sealed class RayTracer : IDisposable {
         Native.Check(Native.rt_create(nGpus, out _ctx), IntPtr.Zero);
         // the reference's Tick counts no rays: the display loop runs without the library's work counters
         Native.Check(Native.rt_set_counting(_ctx, 0), _ctx);
+        // RT_SAMPLES=2|4|8: k x k supersampling resolved on the GPU (the frame handed to the window keeps its size)
+        int samples = int.TryParse(Environment.GetEnvironmentVariable("RT_SAMPLES"), out int k) ? k : 1;
+        Native.Check(Native.rt_set_supersampling(_ctx, samples), _ctx);
         // the hard-coded scene of RayTracer.cs:441-469
         static Native.Vec3 V(float x, float y, float z) => new(x, y, z);
         static Native.Material M(Native.Vec3 kd, Native.Vec3 ka, Native.Vec3 ks, float n, Native.Vec3 km) =>

@@ -251,6 +251,7 @@ struct rt_ctx {
     rt_camera view_cam{};
     int view_w = 0, view_h = 0, view_rows = 0;
     int view_height = 0;  // rt_set_view_height: the view's height (0: each render's own frame height)
+    int ss_log2 = 0;      // rt_set_supersampling: log2 of the factor k (0: off)
     LaunchParams view_lp{};
 };
 
@@ -512,9 +513,11 @@ void copy_view(const LaunchParams& from, LaunchParams& to) {
 }
 
 // The view of a W x VH frame (VH: rt_set_view_height, else H), of which a render traces rows [0, H).
-int view_params(rt_ctx* ctx, int W, int H, LaunchParams& lp) {
-    const int VH = ctx->view_height > 0 ? ctx->view_height : H;
-    if (H > VH) return fail(ctx, RT_ERR_INVALID_ARG, "frame height %d above the view height %d", H, VH);
+// ss > 0 (supersampling, log2 of the factor): W and H arrive in samples, and so does the view height here.
+int view_params(rt_ctx* ctx, int W, int H, LaunchParams& lp, int ss = 0) {
+    const int VH = ctx->view_height > 0 ? ctx->view_height << ss : H;
+    if (H > VH)
+        return fail(ctx, RT_ERR_INVALID_ARG, "frame height %d above the view height %d", H >> ss, ctx->view_height);
     if (ctx->view_ok && ctx->view_w == W && ctx->view_h == VH && ctx->view_rows == H &&
         std::memcmp(&ctx->view_cam, &ctx->cam, sizeof ctx->cam) == 0) {
         copy_view(ctx->view_lp, lp);
@@ -570,8 +573,8 @@ void scene_params(const rt_ctx* ctx, const Device& d, LaunchParams& lp) {
 // division): lx[x] = ((float)x / W - 0.5f) * pw, ly[y] = ((float)y / H - 0.5f) * ph.
 // Rebuilt only when the frame size or view-plane size changes; frames in flight may read
 // the old table, so the device is synchronised first.
-int view_tables(rt_ctx* ctx, Device& d, LaunchParams& lp) {
-    const int VH = ctx->view_height > 0 ? ctx->view_height : lp.H;  // the view's height (ly of row y)
+int view_tables(rt_ctx* ctx, Device& d, LaunchParams& lp, int ss = 0) {
+    const int VH = ctx->view_height > 0 ? ctx->view_height << ss : lp.H;  // the view's height (ly of row y)
     if (d.tab_w != lp.W || d.tab_h != VH || d.tab_pw != lp.pw || d.tab_ph != lp.ph || !d.d_view_tab) {
         std::vector<float> t((size_t)lp.W + (size_t)VH);
         for (int x = 0; x < lp.W; ++x) {
@@ -757,27 +760,42 @@ struct EncTarget {
 
 // Launch the trace of bands (first, step) of `band_rows` rows (at most max_bands of them) into `out` on
 // device d.  `slice`: a Tick hand-off (CopyJob) that rides in the launch as its copy slice.
+// Supersampling (rt_set_supersampling, k = 1 << ss > 1): the arguments are in output pixels as ever, and so
+// is everything the callers do with the output (band sets, hand-offs, gathers); the launch itself works on
+// the k W x k H sample frame -- the same bands, each k times as many sample rows -- and its epilogue writes
+// one output pixel per k x k block (LaunchParams::ss_log2).  check_ctx bounds k W * k H.
 int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, int band_rows, int first, int step,
                 int32_t* out, int* n_bands, int fmt = RT_BANDS_INT32, int n_frames = 1, size_t frame_bytes = 0,
                 const EncTarget* enc = nullptr, const CopyJob* slice = nullptr, int max_bands = INT_MAX) {
+    const int ss = ctx->ss_log2;
+    if (ss > 0 && enc) return fail(ctx, RT_ERR_UNSUPPORTED, "the fused tile encoder does not supersample");
     LaunchParams lp;
     std::memset(&lp, 0, sizeof lp);
-    int rc = view_params(ctx, W, H, lp);
+    int rc = view_params(ctx, W << ss, H << ss, lp, ss);
     if (rc != RT_OK) return rc;
     scene_params(ctx, d, lp);
-    rc = view_tables(ctx, d, lp);
+    rc = view_tables(ctx, d, lp, ss);
     if (rc != RT_OK) return rc;
     const int nb = std::min(bands_of(H, band_rows, first, step), max_bands);
     if (n_bands) *n_bands = nb;
-    lp.band_rows = band_rows, lp.band_first = first, lp.band_step = step;
-    lp.local_rows = nb * band_rows;
+    lp.band_first = first, lp.band_step = step;
+    if (ss > 0) {
+        // (a band of H rows or more is the frame as band 0 whatever its size: k band_rows stays below k H)
+        lp.band_rows = std::min(band_rows, H) << ss;
+        lp.local_rows = nb * lp.band_rows;
+        lp.ss_log2 = ss;
+    } else {
+        lp.band_rows = band_rows;
+        lp.local_rows = nb * band_rows;
+    }
     lp.out = out;
     lp.out_fmt = fmt;
     lp.n_frames = n_frames;
     lp.out_frame_bytes = frame_bytes;
     // single-frame launches of a whole frame on the direct kernel: the dispatch order (order_pick)
     const bool with_copy = slice && slice->words;
-    const bool whole = !enc && !with_copy && band_rows >= lp.local_rows && lp.local_rows == H;
+    // (supersampling launches are never lone: natural tile order, one tile per workgroup)
+    const bool whole = ss == 0 && !enc && !with_copy && band_rows >= lp.local_rows && lp.local_rows == H;
     const bool lone = n_frames <= 1 && whole && lp.S < CULL_MIN_SPHERES && lp.row_order_n == (H + 7) / 8;
     // the bundle kernel's all-lights-ok merged instantiation (C4/C5): natural or measured tile order
     const SceneLayout& L = ctx->layout;
@@ -822,16 +840,21 @@ int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, int ba
     ctx->launches++;
     for (int k = 0; k < nb && ctx->counting; ++k) {  // pixels of rows < H in the launched bands (counted launches)
         const long long y0 = (long long)(first + k * step) * band_rows;
-        ctx->prim_rays += (uint64_t)std::min<long long>(band_rows, (long long)H - y0) * (uint64_t)W * (uint64_t)n_frames;
+        ctx->prim_rays += ((uint64_t)std::min<long long>(band_rows, (long long)H - y0) * (uint64_t)W * (uint64_t)n_frames)
+                          << (2 * ss);  // (supersampling: samples)
     }
     return RT_OK;
 }
 
-int check_ctx(rt_ctx* ctx, int W, int H) {
+// `sampled`: a render that supersamples (its k W x k H sample frame is bounded like any frame).
+int check_ctx(rt_ctx* ctx, int W, int H, bool sampled = true) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "NULL context");
     if (!ctx->has_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_set_scene has not been called");
     if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31) - 1)
         return fail(ctx, RT_ERR_INVALID_ARG, "invalid frame size %dx%d", W, H);
+    if (sampled && ctx->ss_log2 > 0 && (((long long)W << ctx->ss_log2) * ((long long)H << ctx->ss_log2)) > (1LL << 31) - 1)
+        return fail(ctx, RT_ERR_INVALID_ARG, "frame size %dx%d at supersampling factor %d exceeds 2^31 - 1 samples", W, H,
+                    1 << ctx->ss_log2);
     return RT_OK;
 }
 
@@ -1531,6 +1554,20 @@ int rt_set_view_height(rt_ctx* ctx, int view_height) {
     return RT_OK;
 }
 
+int rt_set_supersampling(rt_ctx* ctx, int k) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_set_supersampling: NULL context");
+    if (k != 1 && k != 2 && k != 4 && k != 8)
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_set_supersampling: factor %d is not 1, 2, 4 or 8", k);
+    ctx->ss_log2 = k == 8 ? 3 : k == 4 ? 2 : k == 2 ? 1 : 0;
+    return RT_OK;
+}
+
+int rt_get_supersampling(const rt_ctx* ctx, int* out_k) {
+    if (!ctx || !out_k) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_get_supersampling: NULL argument");
+    *out_k = 1 << ctx->ss_log2;
+    return RT_OK;
+}
+
 int rt_set_camera(rt_ctx* ctx, const rt_camera* camera) {
     if (!ctx || !camera) return fail(ctx, RT_ERR_INVALID_ARG, "rt_set_camera: NULL argument");
     ctx->cam = *camera;
@@ -1789,8 +1826,10 @@ int rt_encode_bands(rt_ctx* ctx, int width, int height, int band_rows, int rank,
 
 int rt_render_bands_tiles(rt_ctx* ctx, int width, int height, int band_rows, int rank, int world, int frame0,
                           int n_frames, int batch_frames, void* d_wire, void* hip_stream) {
-    int rc = check_ctx(ctx, width, height);
+    int rc = check_ctx(ctx, width, height, false);
     if (rc != RT_OK) return rc;
+    if (ctx->ss_log2 > 0)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_render_bands_tiles does not supersample (rt_set_supersampling(ctx, 1) first)");
     rtk::CodecGeom g;
     if (!codec_geom(width, height, band_rows, world, batch_frames, g, nullptr) || rank < 0 || rank >= world ||
         frame0 < 0 || n_frames <= 0 || n_frames > 65535 || frame0 + n_frames > batch_frames || !d_wire ||
@@ -2224,7 +2263,7 @@ int rt_wait(rt_ctx* ctx) {
 // Debug ray view: re-trace every sample_stride-th pixel and append its segments.
 int rt_debug_segments(rt_ctx* ctx, int width, int height, int sample_stride, rt_segment* out, int capacity,
                       int* out_count) {
-    int rc = check_ctx(ctx, width, height);
+    int rc = check_ctx(ctx, width, height, false);  // (the supersampling factor plays no part here)
     if (rc != RT_OK) return rc;
     if (sample_stride <= 0 || capacity < 0 || (capacity > 0 && !out) || !out_count)
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_debug_segments: bad arguments");
@@ -2352,8 +2391,10 @@ int rt_reset_stats(rt_ctx* ctx) {
 }
 
 int rt_count_work(rt_ctx* ctx, int width, int height, rt_work* out) {
-    int rc = check_ctx(ctx, width, height);
+    int rc = check_ctx(ctx, width, height, false);
     if (rc != RT_OK) return rc;
+    if (ctx->ss_log2 > 0)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_count_work does not supersample (rt_set_supersampling(ctx, 1) first)");
     if (!out) return fail(ctx, RT_ERR_INVALID_ARG, "rt_count_work: NULL out_work");
     if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_INVALID_ARG, "rt_count_work needs a single-GPU context");
     Device& d = ctx->dev[0];

@@ -219,6 +219,11 @@ struct LaunchParams {
     // tile_cost: when set, each wave stores its duration (RTC ticks) at tile ty * tiles_x + tx
     const uint32_t* tile_order;
     uint32_t* tile_cost;
+    // supersampling (rt_set_supersampling): log2 of the factor k, 0 = off.  With it set W, H, band_rows and
+    // local_rows above are in samples (the k W x k H frame: view tables, screen boxes and culls as for any
+    // frame of that size), and the output -- one pixel per k x k block, row stride W >> ss_log2 -- is
+    // written by the SS instantiations' epilogue (rt_kernel.hip resolve_tile).  Last: no other field moves.
+    int ss_log2;
 };
 // Tiles per workgroup of the direct kernel's single-frame launches (8: +2.5 % on C2,
 // profiles/r04_final_check.txt); the measured tile order (LaunchParams::tile_order) is padded to it.

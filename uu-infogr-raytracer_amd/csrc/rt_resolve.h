@@ -1,0 +1,38 @@
+// rt_resolve.h -- per-lane arithmetic of the supersampling resolve (rt_set_supersampling), shared by
+// the trace kernels' epilogue (rt_kernel.hip resolve_tile) and host code (tests/native/ss_host.cpp).
+//
+// An output pixel at factor k = 1 << s (s = 1, 2, 3) is, per 8-bit channel, the round-half-up mean of
+// its k x k samples after ShiftColor: (sum + k*k/2) >> 2s.  A sample 0x00RRGGBB is unpacked into two
+// words of 16-bit fields -- {R, B} and {G} -- so that a channel's sum of up to 64 samples (64 * 255 =
+// 16,320 < 2^14) never carries into its neighbour; sums of unpacked samples are plain 32-bit adds (the
+// kernel's cross-lane steps), and the rounding works on both fields of a word at once.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define RT_RESOLVE_FN __host__ __device__ inline
+#else
+#define RT_RESOLVE_FN inline
+#endif
+
+namespace rtk {
+
+struct ResolveSum {
+    uint32_t rb;  // R sum in bits 16-31, B sum in bits 0-15
+    uint32_t g;   // G sum in bits 0-15
+};
+
+RT_RESOLVE_FN ResolveSum resolve_unpack(uint32_t px) { return ResolveSum{px & 0x00ff00ffu, (px >> 8) & 0xffu}; }
+
+RT_RESOLVE_FN ResolveSum resolve_add(ResolveSum a, ResolveSum b) { return ResolveSum{a.rb + b.rb, a.g + b.g}; }
+
+// The sum of (1 << s)^2 unpacked samples -> the output pixel 0x00RRGGBB.
+RT_RESOLVE_FN uint32_t resolve_round(ResolveSum sum, int s) {
+    const int sh = 2 * s;
+    const uint32_t half = (1u << sh) >> 1;  // k*k/2 (s = 0: 0, the sample itself)
+    const uint32_t rb = ((sum.rb + (half | (half << 16))) >> sh) & 0x00ff00ffu;  // (R's low bits fall into B's field: masked)
+    const uint32_t g = ((sum.g + half) >> sh) & 0xffu;
+    return rb | (g << 8);
+}
+
+}  // namespace rtk

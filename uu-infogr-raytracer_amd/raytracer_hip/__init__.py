@@ -16,13 +16,14 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi, debugview, scenes
+from . import abi, debugview, scenes, supersample
 from .abi import RayTracerError, check, load_library
 from .debugview import SEGMENT_DTYPE, DebugView, surface_line, surface_print
 from .dist import bands_of
 
 __all__ = ["Surface", "RayTracer", "Context", "RayTracerError", "scenes", "abi", "load_library",
-           "device_count", "camera_view", "wire_layout", "bands_of", "DebugView", "SEGMENT_DTYPE", "debugview"]
+           "device_count", "camera_view", "wire_layout", "bands_of", "DebugView", "SEGMENT_DTYPE", "debugview",
+           "supersample"]
 
 
 def device_count() -> int:
@@ -126,6 +127,18 @@ class Context:
         """rt_set_counting (ABI 10): False = the trace launches count no rays (a display loop's setting; the
         pixels are the same), True = every launch adds its rays to stats() (the default)."""
         self._check(self.lib.rt_set_counting(self.ptr, 1 if on else 0))
+
+    def set_supersampling(self, k: int):
+        """rt_set_supersampling: k = 1 (off), 2, 4 or 8 samples per pixel and axis, resolved in the trace kernels;
+        every size and band argument of the render calls stays in output pixels (supersample.box_resolve is the
+        definition)."""
+        self._check(self.lib.rt_set_supersampling(self.ptr, int(k)))
+
+    @property
+    def supersampling(self) -> int:
+        k = C.c_int(0)
+        self._check(self.lib.rt_get_supersampling(self.ptr, C.byref(k)))
+        return k.value
 
     def get_camera(self) -> abi.rt_camera:
         c = abi.rt_camera()
@@ -295,13 +308,14 @@ class RayTracer:
     `scene` defaults to the reference's hard-coded scene (RayTracer.cs:441-490).
     `debug=True` is the reference's DEBUG_ENABLE build: Tick() also composites the top-down
     ray inset (raytracer_hip.debugview) into the bottom-right corner of the frame.
+    `samples` = 2, 4 or 8: every Tick() is supersampled k x k (Context.set_supersampling); the frame keeps its size.
     """
 
     _KEYS = {"W": abi.RT_KEY_W, "A": abi.RT_KEY_A, "S": abi.RT_KEY_S, "D": abi.RT_KEY_D,
              "Space": abi.RT_KEY_SPACE, "LeftShift": abi.RT_KEY_SHIFT, "RightShift": abi.RT_KEY_SHIFT}
 
     def __init__(self, screen: Surface, scene: scenes.Scene | None = None, n_gpus: int = 1,
-                 debug: bool = False, debug_seed: int = 0):
+                 debug: bool = False, debug_seed: int = 0, samples: int = 1):
         self.screen = screen
         self.debug = debug
         self._debug_seed = debug_seed
@@ -309,6 +323,7 @@ class RayTracer:
         sc = scene or scenes.reference(screen.width, screen.height)
         self._scene = sc
         self._ctx.set_scene(sc)
+        self._ctx.set_supersampling(samples)
         self._camera = sc.c_camera()
         self._ctx.register_host(screen.pixels)  # pin Surface.pixels once (D2H lands in it)
 
