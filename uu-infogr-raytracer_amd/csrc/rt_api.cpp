@@ -202,6 +202,7 @@ struct SceneLayout {
     size_t off_sph = 0, off_mat = 0, off_pl = 0, off_li = 0, off_cull = 0, off_shcull = 0, bytes = 0;
     size_t off_shg = 0, off_shgrid = 0, off_shslab = 0, off_clus = 0, off_shpre = 0;
     bool has_shpre = false;  // the direct kernel's shadow pre-test records (DevShadowCull [L][S + (S & 1)])
+    bool mirror_box = true;  // the direct kernel's mirrored screen boxes (view_mirror_boxes); RT_MIRROR_BOX=0: off
     int n_clus = 0;  // DevCluster records (the bundle kernel's per-lane pre-cull), 0: none
     bool has_shcull = false;
     bool has_shg = false;  // per-light shadow grids (DevShadowGrid) for the merged shadow pass
@@ -414,7 +415,8 @@ int bands_of(int H, int band_rows, int first, int step) {
 // lx / lz in [tan(phi - g), tan(phi + g)], phi = atan2(cx, cz), g = asin(rho / |(cx, cz)|),
 // valid when cz > rho (sphere strictly in front); same for y with (cy, cz).  Two pixels of
 // slack cover the binary32 pixel-to-direction mapping and the basis' non-orthogonality.
-PrimBox prim_box(const LaunchParams& lp, const DevSphere& s) {
+// extra: added to rho (the mirrored boxes' allowances, mirror_boxes; 0 for the primary boxes).
+PrimBox prim_box(const LaunchParams& lp, const DevSphere& s, double extra = 0.0) {
     const PrimBox all{INT_MIN / 2, INT_MAX / 2, INT_MIN / 2, INT_MAX / 2};
     const double pw = lp.pw, ph = lp.ph, lz = lp.nearc;
     if (!(pw > 0) || !(ph > 0) || !(lz > 0) || !std::isfinite(pw) || !std::isfinite(ph) || !std::isfinite(lz))
@@ -428,7 +430,7 @@ PrimBox prim_box(const LaunchParams& lp, const DevSphere& s) {
     const double dir_err = 0x1p-20 * (camlen + dmax) / lz + 0x1p-20;
     const double r = std::sqrt((double)s.r2);
     if (!std::isfinite(ulen) || !std::isfinite(r) || !(dir_err <= 0x1p-12)) return all;
-    const double rho = (r * (1.0 + 0x1p-8) + (0x1p-8 + 0x1p-20 + dir_err) * ulen) * (1.0 + 0x1p-16) + 0x1p-60;
+    const double rho = (r * (1.0 + 0x1p-8) + (0x1p-8 + 0x1p-20 + dir_err) * ulen) * (1.0 + 0x1p-16) + 0x1p-60 + extra;
     auto fdot = [](const float* a, const float* b) { return (double)a[0] * b[0] + (double)a[1] * b[1] + (double)a[2] * b[2]; };
     const double ortho = std::fabs(fdot(lp.right, lp.up)) + std::fabs(fdot(lp.right, lp.fwd)) +
                          std::fabs(fdot(lp.up, lp.fwd)) + std::fabs(fdot(lp.right, lp.right) - 1.0) +
@@ -454,7 +456,105 @@ PrimBox prim_box(const LaunchParams& lp, const DevSphere& s) {
     return b;
 }
 
-// Order of a single-frame launch's tile rows (LaunchParams::row_order).  The launch's last waves set
+// Mirrored screen boxes (LaunchParams::mbox; the direct kernel's first reflected segment; culling only).
+//
+// A ray reflected by the plane q = {x : n.x = cn} extends backwards through the camera's mirror image, so the
+// reflected line of pixel (x, y) passes sphere i (centre C) at the distance at which the pixel's primary line,
+// continued through q, passes the mirrored centre C' = C - 2 n (n.C - cn) / n.n.  The box is prim_box of (C', r)
+// with rho grown by `extra`, which covers what the binary32 chain adds between the two lines for a lane whose
+// primary hit on q has t <= t_max (eps = 2^-24, E the camera, |d| <= 1 + 2^-20, U = |E| + |cn| / |n| + 2 t_max):
+//   * hp = fl(E + fl(d t)) lies within dh = 4 eps U of the primary line (two roundings per component);
+//   * hp lies within dp = 16 eps U + dh of q: with t = fl(num_f / den_f), n.(E + d t) - cn = t (den - den_f) +
+//     (num_f - num) + the quotient's rounding t eps den_f exactly (no first-order step: a grazing den does not
+//     matter), num_f and den_f each three products and three sums of terms bounded by |E| |n| + |cn| and |d| |n|;
+//     mirroring about the plane through hp instead of q moves C' by 2 dp;
+//   * the binary32 reflection d' = fl(d - n fl(2 fl(d.n))) mirrored back differs from d by at most
+//     2 |n.n - 1| + 12 eps <= 2^-18 (the reference reflects about the raw normal: |n.n - 1| <= 2^-20 is required),
+//     an angle below 2^-16, which moves the line by at most 2^-16 |C' - hp| at C';
+//   * the cull rule itself (rt_kernel.hip, "Wave-level ray bundles": not selectable when the line passes C at
+//     r (1 + 2^-8) + 2^-8 |C - hp| or more) asks for 2^-8 |C - hp|, and |C - hp| <= |C' - E| + |hp - E| + 2 dp
+//     with |hp - E| <= 1.001 t_max; prim_box supplies the 2^-8 |C' - E| part.
+// t_max = MIRROR_TMAX_FACTOR max_i (|C'_i - E| + r_i): the 2^-8 t_max term grows every box in proportion to t_max,
+// while the lanes beyond it (full test) lie within atan(h / t_max) of the plane's horizon, in inverse proportion.
+// A host model of C3's 1080p frame (8x8 tiles, these boxes) counts the sphere pairs a wave's first reflected
+// segment runs, 4 without boxes: 0.92 at factor 0.5, 0.78 at 1, 0.75 at 1.5 and at 2, 0.78 at 3, 0.83 at 4, 0.99
+// at 8 -- a flat optimum; 2 (two tile rows under the horizon take the full test, rho grows by 0.8 % of the
+// farthest mirrored sphere's distance).  No table (the plane's lanes take every sphere) when |n.n - 1| > 2^-20, an input is not finite, or
+// no sphere has a usable record; a sphere with r^2 < 2^-100 or |C' - E| + t_max > 2^40 keeps the box "all" (the
+// cull rule's own domain), as does one that fails prim_box's preconditions.
+// margins = false (the host check's teeth, tests/native/mirror_box_host.cpp): extra = 0 and no t_max.
+constexpr double MIRROR_TMAX_FACTOR = 2.0;
+bool mirror_boxes(const LaunchParams& lp, const DevPlane& q, const std::vector<DevSphere>& sph, PrimBox* box,
+                  float* t_max_out, bool margins = true, double tmax_factor = MIRROR_TMAX_FACTOR) {
+    const PrimBox all{INT_MIN / 2, INT_MAX / 2, INT_MIN / 2, INT_MAX / 2};
+    const size_t S = sph.size();
+    for (size_t i = 0; i < S; ++i) box[i] = all;
+    const double n[3] = {q.nx, q.ny, q.nz}, E[3] = {lp.cam[0], lp.cam[1], lp.cam[2]}, cn = q.cn;
+    const double nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+    if (!(std::fabs(nn - 1.0) <= 0x1p-20) || !std::isfinite(cn)) return false;
+    const double elen = std::sqrt(E[0] * E[0] + E[1] * E[1] + E[2] * E[2]);
+    if (!std::isfinite(elen)) return false;
+    std::vector<DevSphere> mir(S);
+    std::vector<double> ulen(S);
+    double far = 0.0;
+    for (size_t i = 0; i < S; ++i) {
+        const double C[3] = {sph[i].cx, sph[i].cy, sph[i].cz};
+        const double k = 2.0 * (n[0] * C[0] + n[1] * C[1] + n[2] * C[2] - cn) / nn;
+        const double M[3] = {C[0] - k * n[0], C[1] - k * n[1], C[2] - k * n[2]};
+        // the mirrored centre as floats (prim_box reads a DevSphere); its rounding, <= 2 eps |C'|, goes into extra
+        mir[i] = DevSphere{(float)M[0], (float)M[1], (float)M[2], sph[i].r2};
+        const double u[3] = {M[0] - E[0], M[1] - E[1], M[2] - E[2]};
+        ulen[i] = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+        const double reach = ulen[i] + std::sqrt((double)sph[i].r2);
+        if (std::isfinite(reach)) far = std::max(far, reach);
+    }
+    const double t_max = margins ? tmax_factor * far : (double)INFINITY;
+    if (margins && !(t_max > 0.0 && t_max <= 0x1p40)) return false;
+    const double eps = 0x1p-24;
+    const double U = elen + std::fabs(cn) / std::sqrt(nn) + 2.0 * t_max;
+    const double dh = 4.0 * eps * U, dp = 16.0 * eps * U + dh;
+    for (size_t i = 0; i < S; ++i) {
+        if (!std::isfinite(ulen[i]) || !(sph[i].r2 >= 0x1p-100f)) continue;
+        double extra = 0.0;
+        if (margins) {
+            if (!(ulen[i] + t_max <= 0x1p40)) continue;
+            const double mlen = std::sqrt((double)mir[i].cx * mir[i].cx + (double)mir[i].cy * mir[i].cy + (double)mir[i].cz * mir[i].cz);
+            extra = 0x1p-8 * (1.001 * t_max + 2.0 * dp) + dh + 2.0 * dp + 0x1p-16 * (ulen[i] + 1.001 * t_max + 2.0 * dp) +
+                    2.0 * eps * mlen * (1.0 + 0x1p-8);
+            extra *= 1.0 + 0x1p-10;
+        }
+        box[i] = prim_box(lp, mir[i], extra);
+    }
+    // (the largest float not above t_max: a lane compares its binary32 t against it)
+    float tm = margins ? (float)t_max : INFINITY;
+    if (margins && (double)tm > t_max) tm = std::nextafter(tm, 0.0f);
+    *t_max_out = tm;
+    return true;
+}
+
+// The tables of a view: the first MIRROR_BOX_PLANES planes with a mirror material, those whose table can be built.
+void view_mirror_boxes(LaunchParams& lp, const SceneLayout& L) {
+    lp.mbox_n = 0;
+    for (int k = 0; k < MIRROR_BOX_PLANES; ++k) {
+        lp.mbox_plane[k] = -1, lp.mbox_tmax[k] = 0.0f;
+        for (int i = 0; i < CULL_MIN_SPHERES; ++i) lp.mbox[k][i] = PrimBox{INT_MIN / 2, INT_MAX / 2, INT_MIN / 2, INT_MAX / 2};
+    }
+    if (!L.mirror_box || !lp.prim_const || L.S < 1 || L.S >= CULL_MIN_SPHERES || L.limit < 1) return;
+    if (L.host_blob.size() < L.off_mat + sizeof(DevMaterial) * (size_t)(L.S + L.P)) return;
+    const DevMaterial* mat = (const DevMaterial*)(L.host_blob.data() + L.off_mat);
+    int mirrors = 0;
+    for (int j = 0; j < L.P && mirrors < MIRROR_BOX_PLANES; ++j) {
+        if (!(mat[L.S + j].flags & MAT_MIRROR)) continue;
+        ++mirrors;
+        const int k = lp.mbox_n;
+        if (mirror_boxes(lp, L.host_pl[(size_t)j], L.host_sph, lp.mbox[k], &lp.mbox_tmax[k])) {
+            lp.mbox_plane[k] = j;
+            ++lp.mbox_n;
+        }
+    }
+}
+
+// Order of a single-frame launch's tile rows (LaunchParams::row_order). The launch's last waves set
 // its tail, so the expensive rows should start first and the cheap ones come last.  A tile row's cost
 // is estimated from eight primary rays through its middle pixel row: 1 for a ray that meets nothing,
 // 1 + L when it meets a plane in front of the camera or falls inside a diffuse sphere's screen box
@@ -507,6 +607,10 @@ void copy_view(const LaunchParams& from, LaunchParams& to) {
     to.prim_const = from.prim_const;
     std::memcpy(to.pc, from.pc, sizeof to.pc);
     std::memcpy(to.pbox, from.pbox, sizeof to.pbox);
+    to.mbox_n = from.mbox_n;
+    std::memcpy(to.mbox_plane, from.mbox_plane, sizeof to.mbox_plane);
+    std::memcpy(to.mbox_tmax, from.mbox_tmax, sizeof to.mbox_tmax);
+    std::memcpy(to.mbox, from.mbox, sizeof to.mbox);
     to.row_order_n = from.row_order_n;
     to.col_major = from.col_major;
     std::memcpy(to.row_order, from.row_order, sizeof(uint16_t) * (size_t)from.row_order_n);
@@ -541,6 +645,7 @@ int view_params(rt_ctx* ctx, int W, int H, LaunchParams& lp, int ss = 0) {
             lp.pc[i] = PrimConst{oc.x, oc.y, oc.z, hdot(oc, oc) - sph[i].r2};
             lp.pbox[i] = prim_box(lp, sph[i]);
         }
+    view_mirror_boxes(lp, ctx->layout);  // (lp.H = VH: in the view's pixels, like pbox)
     lp.row_order_n = row_order(lp, ctx->layout, lp.row_order);  // dispatch-order candidate 0 (order_pick)
     lp.H = H;  // the rows traced (validity, band counts); a cut view's row order no longer matches: not lone
     copy_view(lp, ctx->view_lp);
@@ -1445,6 +1550,9 @@ int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_
     // the direct kernel's shadow pre-test (S < CULL_MIN_SPHERES); RT_SHADOW_PRE=0 turns it off (A/B)
     const char* pv = std::getenv("RT_SHADOW_PRE");
     L.has_shpre = n_spheres < CULL_MIN_SPHERES && n_lights >= 1 && !(pv && std::strcmp(pv, "0") == 0);
+    // the direct kernel's mirrored screen boxes, built per view (view_mirror_boxes); RT_MIRROR_BOX=0 turns them off (A/B)
+    const char* mv = std::getenv("RT_MIRROR_BOX");
+    L.mirror_box = !(mv && std::strcmp(mv, "0") == 0);
     L.bytes = al(L.off_shpre + (L.has_shpre ? sizeof(DevShadowCull) * (size_t)n_lights * (size_t)s_pad : 0)) + 256;
 
     std::vector<unsigned char> blob(L.bytes, 0);

@@ -224,7 +224,16 @@ struct LaunchParams {
     // frame of that size), and the output -- one pixel per k x k block, row stride W >> ss_log2 -- is
     // written by the SS instantiations' epilogue (rt_kernel.hip resolve_tile).  Last: no other field moves.
     int ss_log2;
+    // Mirrored screen boxes (the direct kernel, S < CULL_MIN_SPHERES, limit >= 1; culling only): for the first
+    // MIRROR_BOX_PLANES mirror planes whose table could be built (mbox_n of them, plane index mbox_plane[k]),
+    // mbox[k][i] is the screen box outside which a ray reflected by that plane at a primary hit with
+    // t <= mbox_tmax[k] cannot select sphere i (rt_api.cpp mirror_boxes; in the view's pixels like pbox).
+    int mbox_n;
+    int mbox_plane[2];
+    float mbox_tmax[2];
+    PrimBox mbox[2][CULL_MIN_SPHERES];
 };
+constexpr int MIRROR_BOX_PLANES = 2;
 // Tiles per workgroup of the direct kernel's single-frame launches (8: +2.5 % on C2,
 // profiles/r04_final_check.txt); the measured tile order (LaunchParams::tile_order) is padded to it.
 constexpr int SINGLE_WPG = 4;
