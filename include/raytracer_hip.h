@@ -269,6 +269,43 @@ int rt_render_bands_ex(rt_ctx* ctx, int width, int height, int band_rows, int ba
 int rt_render_bands_batch(rt_ctx* ctx, int width, int height, int band_rows, int band_first,
                           int band_step, int n_frames, void* d_out, size_t frame_stride_bytes,
                           int format, void* hip_stream, int* out_n_bands);
+/* (ABI 10 addition) Camera paths: one batch launch, one camera per frame -- an offline render of a camera
+ * move (a fly-through, a turntable, a stereo pair, recorded input) at the batch launch's rate.
+ * rt_render_path_bands: frame f = the frame rt_render_bands_ex would write with camera cameras[f] set:
+ * this rank's bands of n_frames frames in ONE launch, frame f at (char*)d_out + f * frame_stride_bytes, in
+ * `format` (RT_BANDS_INT32 / RGB24 / FRAME).  Asynchronous on hip_stream.
+ *   - `cameras` is host memory, consumed before the call returns (the caller may reuse it at once).  The
+ *     context's own camera (rt_set_camera) is neither read nor changed: a later rt_render renders it as ever.
+ *   - rt_set_view_height applies to every frame, exactly as for rt_render_bands_batch.
+ *   - Arguments are checked as rt_render_bands_batch checks them (single-GPU contexts only, band_rows > 0,
+ *     frame_stride_bytes no smaller than a frame's output when n_frames > 1, ...); a NULL `cameras` or an
+ *     n_frames <= 0 or above RT_MAX_PATH_FRAMES returns RT_ERR_INVALID_ARG.
+ *   - With supersampling on (rt_set_supersampling, k > 1) both calls return RT_ERR_UNSUPPORTED.
+ *   - Statistics: every frame has its own rays and counts for itself -- with rt_set_counting on,
+ *     reflect_rays and shadow_rays grow by the sum over the frames and primary_rays by the traced pixels x
+ *     n_frames; frames, pixels and launches behave as for rt_render_bands_batch.  With counting off the
+ *     kernels count nothing (recommended for path renders that never read the counts: a counting path
+ *     launch makes an atomic pair per wave per frame where the one-camera batch makes one per launch).
+ *   - Path launches always run in natural tile order, one tile per workgroup: the lone-frame tuner
+ *     (rt_dispatch_order) is not involved, even at n_frames == 1.
+ * rt_render_path: whole frames into host memory, pixels[n_frames][height][width] (0x00RRGGBB).
+ * Synchronous.  It traces into context-owned device buffers in launches of at most RT_PATH_CHUNK_FRAMES
+ * frames (default: as many as keep a buffer at or below 256 MiB, at least 1; the environment variable of
+ * that name, read at rt_create, overrides it) and copies each chunk out with hipMemcpyAsync on a second
+ * stream.  Into a range registered through rt_register_host that copy is asynchronous: chunk c is copied
+ * while chunk c + 1 traces.  Into any other memory the runtime stages the copy and the call blocks the host
+ * until it is done, so the chunks are then traced and copied one after the other -- register `pixels` for
+ * the overlap.  Whatever the call returns, no copy into `pixels` is still pending when it returns.
+ * Memory: the frames' view records (2.5 KB each) pass through four table slots of pinned host and device
+ * memory that the context keeps between calls; a slot that a long path grew (65,535 frames: about 165 MB
+ * pinned and as much on the device) is cut back to the size of the next call that uses it when that call has
+ * at most 256 frames, and everything is released by rt_destroy. */
+#define RT_MAX_PATH_FRAMES 65535   /* grid z */
+int rt_render_path_bands(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames,
+                         int band_rows, int band_first, int band_step, void* d_out,
+                         size_t frame_stride_bytes, int format, void* hip_stream, int* out_n_bands);
+int rt_render_path(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames,
+                   int32_t* pixels);
 /* Reassemble the band sets of `world` ranks (band b rendered by rank b % world with
  * band_first = rank, band_step = world), gathered rank after rank at slot_bytes intervals
  * in d_gathered, into the row-major frame d_frame[height][width] -- one launch for all

@@ -155,6 +155,25 @@ struct Device {
     static constexpr int RING = 16;
     hipEvent_t ev_ring[RING] = {};
     uint64_t frames_issued = 0;
+    // Camera-path launches (rt_render_path_bands): the frames' DevView records go through a ring of table slots
+    // -- pinned staging, hipMemcpyAsync on the caller's stream ahead of the launch, an event after it; a slot is
+    // reused only once its event has completed (waited for on the host), so back-to-back calls on any streams
+    // never overwrite records a queued launch still reads.
+    static constexpr int PATH_SLOTS = 4;
+    static constexpr size_t PATH_SLOT_KEEP = 256;  // DevView records (643 KB) a slot retains between calls
+    struct PathSlot {
+        DevView* h_views = nullptr;  // pinned
+        DevView* d_views = nullptr;
+        size_t cap = 0;              // frames
+        hipEvent_t done = nullptr;   // after the slot's last launch
+        bool busy = false;
+    } path_slot[PATH_SLOTS];
+    unsigned path_next = 0;
+    // rt_render_path: chunk c is traced into d_path[c % 2] (stream) and copied out by the copy engine
+    // (copy_stream) under the trace of chunk c + 1
+    int32_t* d_path[2] = {nullptr, nullptr};
+    size_t path_cap[2] = {0, 0};
+    hipEvent_t ev_path_traced[2] = {}, ev_path_copied[2] = {};
     float* d_view_tab = nullptr;  // lx[W] then ly[H] (view_tables)
     size_t view_tab_cap = 0;
     int tab_w = -1, tab_h = -1;
@@ -235,6 +254,7 @@ struct rt_ctx {
     bool counting = true;  // rt_set_counting: trace launches add to the ray counters
     uint64_t scene_gen = 0;  // rt_set_scene calls (the dispatch-order measurements belong to one scene)
     int order_fixed = -1;    // RT_DISPATCH_ORDER=0/1/2: that candidate for every single-frame launch
+    int path_chunk_frames = 0;  // RT_PATH_CHUNK_FRAMES: frames per launch of rt_render_path (0: by buffer size)
     int tick_inflight = 0;   // rt_render_async: frames queued per worker before the host waits (0: no bound)
     int32_t* host_staging = nullptr;
     // host ranges registered through rt_register_host and their device-mapped addresses (one per
@@ -616,6 +636,8 @@ void copy_view(const LaunchParams& from, LaunchParams& to) {
     std::memcpy(to.row_order, from.row_order, sizeof(uint16_t) * (size_t)from.row_order_n);
 }
 
+int view_fill(rt_ctx* ctx, const rt_camera& cam, int W, int VH, LaunchParams& lp);
+
 // The view of a W x VH frame (VH: rt_set_view_height, else H), of which a render traces rows [0, H).
 // ss > 0 (supersampling, log2 of the factor): W and H arrive in samples, and so does the view height here.
 int view_params(rt_ctx* ctx, int W, int H, LaunchParams& lp, int ss = 0) {
@@ -627,8 +649,23 @@ int view_params(rt_ctx* ctx, int W, int H, LaunchParams& lp, int ss = 0) {
         copy_view(ctx->view_lp, lp);
         return RT_OK;
     }
+    int rc = view_fill(ctx, ctx->cam, W, VH, lp);
+    if (rc != RT_OK) return rc;
+    lp.row_order_n = row_order(lp, ctx->layout, lp.row_order);  // dispatch-order candidate 0 (order_pick)
+    lp.H = H;  // the rows traced (validity, band counts); a cut view's row order no longer matches: not lone
+    copy_view(lp, ctx->view_lp);
+    ctx->view_cam = ctx->cam, ctx->view_w = W, ctx->view_h = VH, ctx->view_rows = H, ctx->view_ok = true;
+    return RT_OK;
+}
+
+// Everything of a W x VH view that depends on the camera, into the view part of lp: position and basis, the
+// view plane (pw, ph, nearc: the same for every camera of one frame size), lp.W / lp.H = the view's size, the
+// primary constants and screen boxes (prim_box) and the mirrored boxes (view_mirror_boxes).  view_params (the
+// context's camera, by value in the kernarg block) and the camera-path calls (one DevView per frame,
+// view_record) both build their views here, so a path frame carries the values a one-camera launch would.
+int view_fill(rt_ctx* ctx, const rt_camera& cam, int W, int VH, LaunchParams& lp) {
     rt_view v;
-    int rc = rt_camera_view(&ctx->cam, W, VH, &v);
+    int rc = rt_camera_view(&cam, W, VH, &v);
     if (rc != RT_OK) return fail(ctx, rc, "invalid frame size %dx%d", W, VH);
     lp.cam[0] = v.position.x, lp.cam[1] = v.position.y, lp.cam[2] = v.position.z;
     lp.right[0] = v.right.x, lp.right[1] = v.right.y, lp.right[2] = v.right.z;
@@ -646,11 +683,23 @@ int view_params(rt_ctx* ctx, int W, int H, LaunchParams& lp, int ss = 0) {
             lp.pbox[i] = prim_box(lp, sph[i]);
         }
     view_mirror_boxes(lp, ctx->layout);  // (lp.H = VH: in the view's pixels, like pbox)
-    lp.row_order_n = row_order(lp, ctx->layout, lp.row_order);  // dispatch-order candidate 0 (order_pick)
-    lp.H = H;  // the rows traced (validity, band counts); a cut view's row order no longer matches: not lone
-    copy_view(lp, ctx->view_lp);
-    ctx->view_cam = ctx->cam, ctx->view_w = W, ctx->view_h = VH, ctx->view_rows = H, ctx->view_ok = true;
     return RT_OK;
+}
+
+// The DevView record of a view built by view_fill (padding zeroed: records compare bytewise).
+void view_record(const LaunchParams& lp, DevView& v) {
+    std::memset(&v, 0, sizeof v);
+    std::memcpy(v.cam, lp.cam, sizeof v.cam);
+    std::memcpy(v.right, lp.right, sizeof v.right);
+    std::memcpy(v.up, lp.up, sizeof v.up);
+    std::memcpy(v.fwd, lp.fwd, sizeof v.fwd);
+    v.prim_const = lp.prim_const;
+    v.mbox_n = lp.mbox_n;
+    std::memcpy(v.mbox_plane, lp.mbox_plane, sizeof v.mbox_plane);
+    std::memcpy(v.mbox_tmax, lp.mbox_tmax, sizeof v.mbox_tmax);
+    std::memcpy(v.pc, lp.pc, sizeof v.pc);
+    std::memcpy(v.pbox, lp.pbox, sizeof v.pbox);
+    std::memcpy(v.mbox, lp.mbox, sizeof v.mbox);
 }
 
 void scene_params(const rt_ctx* ctx, const Device& d, LaunchParams& lp) {
@@ -1183,6 +1232,11 @@ int rt_create_ex(int n_gpus, int flags, rt_ctx** out_ctx) {
     // RT_DISPATCH_ORDER=0/1/2 fixes the single-frame dispatch order (order_pick; A/B and tests)
     if (const char* o = std::getenv("RT_DISPATCH_ORDER"))
         if (o[0] >= '0' && o[0] < '0' + ORDER_CANDIDATES && o[1] == 0) ctx->order_fixed = o[0] - '0';
+    // RT_PATH_CHUNK_FRAMES=1..65535 fixes the frames per launch of rt_render_path (path_chunk_frames)
+    if (const char* q = std::getenv("RT_PATH_CHUNK_FRAMES")) {
+        const int k = std::atoi(q);
+        if (k >= 1 && k <= RT_MAX_PATH_FRAMES) ctx->path_chunk_frames = k;
+    }
     // rt_render_async keeps at most TICK_INFLIGHT frames per worker queued behind the copy engine: with more, one
     // hipMemcpyAsync of the hand-off now and then blocked the host for 6-7 ms (the runtime, not the copy: 5.4-7.0 ms
     // for an 8.3 MB copy that takes 160 us) -- a queued C3 run of 20 frames at 2.1-2.7k fps instead of 5.8k, in
@@ -1247,6 +1301,16 @@ void rt_destroy(rt_ctx* ctx) {
         }
         for (hipEvent_t& ev : d.ev_ring)
             if (ev) (void)hipEventDestroy(ev);
+        for (Device::PathSlot& ps : d.path_slot) {
+            if (ps.done) (void)hipEventDestroy(ps.done);
+            if (ps.h_views) (void)hipHostFree(ps.h_views);
+            if (ps.d_views) (void)hipFree(ps.d_views);
+        }
+        for (int i = 0; i < 2; ++i) {
+            if (d.ev_path_traced[i]) (void)hipEventDestroy(d.ev_path_traced[i]);
+            if (d.ev_path_copied[i]) (void)hipEventDestroy(d.ev_path_copied[i]);
+            if (d.d_path[i]) (void)hipFree(d.d_path[i]);
+        }
         if (d.copy_stream) (void)hipStreamDestroy(d.copy_stream);
         if (d.comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(d.comm);
         if (d.d_scene) (void)hipFree(d.d_scene);
@@ -2250,6 +2314,166 @@ int rt_render(rt_ctx* ctx, int width, int height, int32_t* pixels) {
     }
     ctx->frames++;
     ctx->pixels += (uint64_t)width * (uint64_t)height;
+    return RT_OK;
+}
+
+namespace {
+// Bytes of one frame's output of a band render in `fmt`.
+size_t band_output_bytes(int W, int H, int nb, int band_rows, int fmt) {
+    return fmt == RT_BANDS_FRAME ? (size_t)W * H * 4 : (size_t)nb * band_rows * W * (fmt == RT_BANDS_RGB24 ? 3 : 4);
+}
+
+// The launch of a camera-path call: n_frames frames (grid z), frame f with the view of cams[f].  The views are
+// built on the host by view_fill -- the code behind every one-camera launch -- packed as DevView records into
+// a table slot's pinned staging buffer and uploaded on `stream` ahead of the launch.  The context's camera and
+// its view cache (view_lp) are not touched.  Natural tile order, one tile per workgroup, whatever n_frames.
+// Nothing here waits for the device except a slot's own event; the shared view tables (view_tables) are rebuilt,
+// with that function's synchronisation, only when the frame size changes, and a slot's buffers are reallocated
+// only when a call brings more frames than the slot holds, or finds it holding more than PATH_SLOT_KEEP.
+int trace_path(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const rt_camera* cams, int n_frames,
+               int band_rows, int first, int step, void* out, size_t frame_bytes, int fmt) {
+    const int VH = ctx->view_height > 0 ? ctx->view_height : H;
+    if (H > VH) return fail(ctx, RT_ERR_INVALID_ARG, "frame height %d above the view height %d", H, ctx->view_height);
+    Device::PathSlot& ps = d.path_slot[d.path_next++ % Device::PATH_SLOTS];
+    if (ps.busy) {  // the slot's last launch may still read its records
+        HIP_TRY(ctx, hipEventSynchronize(ps.done));
+        ps.busy = false;
+    }
+    if (!ps.done) HIP_TRY(ctx, hipEventCreateWithFlags(&ps.done, hipEventDisableTiming));
+    // (a slot keeps its buffers for the next call, but no more than PATH_SLOT_KEEP records of them: a call that
+    // needs fewer finds a larger table shrunk to its own size, so one long path does not pin its tables for good)
+    if (ps.cap < (size_t)n_frames || (ps.cap > Device::PATH_SLOT_KEEP && (size_t)n_frames <= Device::PATH_SLOT_KEEP)) {
+        if (ps.h_views) (void)hipHostFree(ps.h_views);
+        if (ps.d_views) (void)hipFree(ps.d_views);
+        ps.h_views = nullptr, ps.d_views = nullptr, ps.cap = 0;
+        const size_t bytes = (size_t)n_frames * sizeof(DevView);
+        hipError_t e = hipHostMalloc((void**)&ps.h_views, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void**)&ps.d_views, bytes);
+        if (e != hipSuccess) {
+            if (ps.h_views) (void)hipHostFree(ps.h_views);
+            ps.h_views = nullptr;
+            return fail(ctx, RT_ERR_OOM, "view table of %d frames: %s", n_frames, hipGetErrorString(e));
+        }
+        ps.cap = (size_t)n_frames;
+    }
+    LaunchParams lp;
+    std::memset(&lp, 0, sizeof lp);
+    for (int f = 0; f < n_frames; ++f) {
+        const int rc = view_fill(ctx, cams[f], W, VH, lp);
+        if (rc != RT_OK) return rc;
+        view_record(lp, ps.h_views[f]);
+    }
+    lp.H = H;  // the rows traced; pw, ph, nearc and W are the same for every camera (lxt / lyt: view_tables)
+    scene_params(ctx, d, lp);
+    int rc = view_tables(ctx, d, lp);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ps.d_views, ps.h_views, (size_t)n_frames * sizeof(DevView), hipMemcpyHostToDevice, stream));
+    const int nb = bands_of(H, band_rows, first, step);
+    lp.views = ps.d_views;
+    lp.band_first = first, lp.band_step = step, lp.band_rows = band_rows, lp.local_rows = nb * band_rows;
+    lp.out = (int32_t*)out;
+    lp.out_fmt = fmt;
+    lp.n_frames = n_frames;
+    lp.out_frame_bytes = frame_bytes;
+    hipStream_t saved = d.stream;
+    d.stream = stream;
+    const bool timed = begin_timed(ctx, d, 0);
+    const int e = launch_trace(lp, ctx->layout.generic_pow, false, stream);
+    end_timed(d, timed);
+    d.stream = saved;
+    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "path launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(ctx, hipEventRecord(ps.done, stream));
+    ps.busy = true;
+    ctx->launches++;
+    for (int k = 0; k < nb && ctx->counting; ++k) {  // pixels of rows < H in the launched bands (counted launches)
+        const long long y0 = (long long)(first + k * step) * band_rows;
+        ctx->prim_rays += (uint64_t)std::min<long long>(band_rows, (long long)H - y0) * (uint64_t)W * (uint64_t)n_frames;
+    }
+    return RT_OK;
+}
+
+int check_path(rt_ctx* ctx, const char* who, int W, int H, const rt_camera* cams, int n_frames) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "NULL context");
+    if (!cams || n_frames <= 0 || n_frames > RT_MAX_PATH_FRAMES)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: NULL cameras or a frame count outside 1..%d", who, RT_MAX_PATH_FRAMES);
+    int rc = check_ctx(ctx, W, H, false);
+    if (rc != RT_OK) return rc;
+    if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s needs a single-GPU context", who);
+    if (ctx->ss_log2 > 0) return fail(ctx, RT_ERR_UNSUPPORTED, "%s does not supersample", who);
+    return RT_OK;
+}
+}  // namespace
+
+int rt_render_path_bands(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames, int band_rows,
+                         int band_first, int band_step, void* d_out, size_t frame_stride_bytes, int format,
+                         void* hip_stream, int* out_n_bands) {
+    int rc = check_path(ctx, "rt_render_path_bands", width, height, cameras, n_frames);
+    if (rc != RT_OK) return rc;
+    if (band_rows <= 0 || band_first < 0 || band_step <= 0 || !d_out ||
+        (format != RT_BANDS_INT32 && format != RT_BANDS_RGB24 && format != RT_BANDS_FRAME))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_path_bands: bad band arguments");
+    const int nb = bands_of(height, band_rows, band_first, band_step);
+    if (n_frames > 1 && frame_stride_bytes < band_output_bytes(width, height, nb, band_rows, format))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_path_bands: frame stride smaller than a frame's output");
+    Device& d = ctx->dev[0];
+    DeviceGuard guard(d.id);
+    rc = trace_path(ctx, d, (hipStream_t)hip_stream, width, height, cameras, n_frames, band_rows, band_first, band_step,
+                    d_out, frame_stride_bytes, format);
+    if (out_n_bands) *out_n_bands = nb;
+    if (rc == RT_OK) ctx->pixels += (uint64_t)nb * band_rows * width * (uint64_t)n_frames;
+    return rc;
+}
+
+// Chunks of at most path_chunk_frames frames: chunk c is traced into d_path[c % 2] on the worker's stream and
+// copied out by the copy engine on copy_stream once its trace event has fired, under the trace of chunk c + 1;
+// the trace of chunk c + 2 waits for that copy (the Tick pattern of tick_sync's chunks, over frames).
+int rt_render_path(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames, int32_t* pixels) {
+    int rc = check_path(ctx, "rt_render_path", width, height, cameras, n_frames);
+    if (rc != RT_OK) return rc;
+    if (!pixels) return fail(ctx, RT_ERR_INVALID_ARG, "NULL pixels");
+    Device& d = ctx->dev[0];
+    if (d.hand.job.words || d.copy_pending[0] || d.copy_pending[1]) {  // rt_render_async frames first
+        rc = rt_wait(ctx);
+        if (rc != RT_OK) return rc;
+    }
+    DeviceGuard guard(d.id);
+    const size_t frame_bytes = (size_t)width * height * sizeof(int32_t);
+    const size_t fit = std::max<size_t>(1, ((size_t)256 << 20) / frame_bytes);
+    const int chunk = (int)std::min<size_t>((size_t)n_frames, ctx->path_chunk_frames > 0 ? (size_t)ctx->path_chunk_frames : fit);
+    const int n_chunks = (n_frames + chunk - 1) / chunk;
+    if (!d.copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking));
+    for (int i = 0; i < std::min(2, n_chunks); ++i) {
+        rc = grow(ctx, (void**)&d.d_path[i], &d.path_cap[i], (size_t)chunk * frame_bytes);
+        if (rc != RT_OK) return rc;
+        if (!d.ev_path_traced[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&d.ev_path_traced[i], hipEventDisableTiming));
+        if (!d.ev_path_copied[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&d.ev_path_copied[i], hipEventDisableTiming));
+    }
+    // Every failure inside the loop leaves through the two synchronisations below: copies already queued into
+    // `pixels` have landed (or failed) before this synchronous call returns, whatever it returns.
+    auto hip_ok = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess) rc = fail(ctx, RT_ERR_HIP, "rt_render_path: %s failed: %s", what, hipGetErrorString(e));
+        return e == hipSuccess;
+    };
+    for (int c = 0; c < n_chunks; ++c) {
+        const int f0 = c * chunk, nf = std::min(chunk, n_frames - f0), b = c & 1;
+        if (c >= 2 && !hip_ok(hipStreamWaitEvent(d.stream, d.ev_path_copied[b], 0), "hipStreamWaitEvent")) break;
+        rc = trace_path(ctx, d, d.stream, width, height, cameras + f0, nf, height, 0, 1, d.d_path[b], frame_bytes,
+                        RT_BANDS_INT32);
+        if (rc != RT_OK) break;
+        // (into a range that is not registered the runtime stages this copy and the call returns only when it is
+        // done: chunk c + 1 is then traced after the copy of chunk c, not under it)
+        if (!hip_ok(hipEventRecord(d.ev_path_traced[b], d.stream), "hipEventRecord") ||
+            !hip_ok(hipStreamWaitEvent(d.copy_stream, d.ev_path_traced[b], 0), "hipStreamWaitEvent") ||
+            !hip_ok(hipMemcpyAsync(pixels + (size_t)f0 * width * height, d.d_path[b], (size_t)nf * frame_bytes,
+                                   hipMemcpyDeviceToHost, d.copy_stream), "hipMemcpyAsync") ||
+            !hip_ok(hipEventRecord(d.ev_path_copied[b], d.copy_stream), "hipEventRecord"))
+            break;
+    }
+    const hipError_t e_trace = hipStreamSynchronize(d.stream), e_copy = hipStreamSynchronize(d.copy_stream);
+    if (rc != RT_OK) return rc;
+    if (!hip_ok(e_trace, "hipStreamSynchronize") || !hip_ok(e_copy, "hipStreamSynchronize")) return rc;
+    ctx->frames += (uint64_t)n_frames;
+    ctx->pixels += (uint64_t)width * (uint64_t)height * (uint64_t)n_frames;
     return RT_OK;
 }
 

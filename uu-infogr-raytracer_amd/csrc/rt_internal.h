@@ -162,6 +162,23 @@ struct CopyJob {
     unsigned pad;
 };
 
+// The view of one frame of a camera-path launch (rt_render_path_bands: LaunchParams::views, one record per
+// grid z in device memory): every LaunchParams field that depends on the camera, with the same values the
+// by-value block of a one-camera launch carries (rt_api.cpp view_fill builds both).  pw / ph / nearc and
+// the lxt / lyt tables depend only on the frame size and are shared by the frames.
+struct alignas(16) DevView {
+    float cam[3], right[3], up[3], fwd[3];
+    int prim_const;
+    int mbox_n;
+    int mbox_plane[2];
+    float mbox_tmax[2];
+    int pad[2];
+    PrimConst pc[MAX_PRIM_CONST];
+    PrimBox pbox[MAX_PRIM_CONST];
+    PrimBox mbox[2][CULL_MIN_SPHERES];
+};
+static_assert(sizeof(DevView) % 16 == 0, "DevView records are 16-byte aligned in their device table");
+
 // Per-launch parameters (passed by value as the kernel argument block, < 4 KiB).
 struct LaunchParams {
     const DevSphere* sph;
@@ -232,6 +249,10 @@ struct LaunchParams {
     int mbox_plane[2];
     float mbox_tmax[2];
     PrimBox mbox[2][CULL_MIN_SPHERES];
+    // Camera-path launches (rt_render_path_bands): frame z of the grid takes its view from views[z] instead of
+    // cam .. fwd, prim_const, pc, pbox and mbox* above (the PATH instantiations, rt_kernel.hip); nullptr: every
+    // frame has the view above.  Last: no other field moves.
+    const DevView* views;
 };
 constexpr int MIRROR_BOX_PLANES = 2;
 // Tiles per workgroup of the direct kernel's single-frame launches (8: +2.5 % on C2,

@@ -16,14 +16,14 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi, debugview, scenes, supersample
+from . import abi, debugview, path, scenes, supersample
 from .abi import RayTracerError, check, load_library
 from .debugview import SEGMENT_DTYPE, DebugView, surface_line, surface_print
 from .dist import bands_of
 
 __all__ = ["Surface", "RayTracer", "Context", "RayTracerError", "scenes", "abi", "load_library",
            "device_count", "camera_view", "wire_layout", "bands_of", "DebugView", "SEGMENT_DTYPE", "debugview",
-           "supersample"]
+           "supersample", "path"]
 
 
 def device_count() -> int:
@@ -185,6 +185,28 @@ class Context:
                                                    C.c_void_p(d_ptr), frame_stride_bytes, fmt, C.c_void_p(stream),
                                                    C.byref(nb)))
         return nb.value
+
+    def render_path_bands(self, width: int, height: int, cameras, band_rows: int, band_first: int, band_step: int,
+                          d_ptr: int, frame_stride_bytes: int, fmt: int = abi.RT_BANDS_INT32, stream: int = 0) -> int:
+        """One frame per camera of `cameras` (a sequence of abi.rt_camera, or path.as_array's array) in one
+        launch: these bands of frame f, seen from cameras[f], at d_ptr + f * frame_stride_bytes
+        (rt_render_path_bands).  The context's own camera is not used."""
+        cams = path.as_array(cameras)
+        nb = C.c_int(0)
+        self._check(self.lib.rt_render_path_bands(self.ptr, width, height, cams, len(cams), band_rows, band_first,
+                                                  band_step, C.c_void_p(d_ptr), frame_stride_bytes, fmt,
+                                                  C.c_void_p(stream), C.byref(nb)))
+        return nb.value
+
+    def render_path(self, cameras, width: int, height: int, out: np.ndarray | None = None) -> np.ndarray:
+        """Whole frames of a camera path into host memory, [n, height, width] (rt_render_path; synchronous)."""
+        cams = path.as_array(cameras)
+        n = len(cams)
+        if out is None:
+            out = np.empty((n, height, width), dtype=np.int32)
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.size == n * width * height
+        self._check(self.lib.rt_render_path(self.ptr, width, height, cams, n, out.ctypes.data))
+        return out.reshape(n, height, width)
 
     def scatter_gathered(self, width: int, height: int, band_rows: int, world: int, d_gathered: int,
                          rank_stride: int, d_frame: int, fmt: int = abi.RT_BANDS_RGB24, stream: int = 0):

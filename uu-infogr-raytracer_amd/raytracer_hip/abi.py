@@ -19,6 +19,7 @@ RT_COMM_ID_BYTES = 128
 RT_CREATE_RCCL_GATHER = 1
 RT_CREATE_SHARED_DEVICE = 2
 RT_MAX_WORKERS = 64
+RT_MAX_PATH_FRAMES = 65535  # rt_render_path_bands / rt_render_path: frames per call (grid z)
 RT_BANDS_INT32, RT_BANDS_RGB24, RT_BANDS_FRAME = 0, 1, 2
 RT_OK = 0
 RT_ERR_INVALID_ARG = -1
@@ -134,6 +135,9 @@ EXPORTS = [
                                      C.c_void_p, C.POINTER(C.c_int)]),
     ("rt_render_bands_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                         C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    ("rt_render_path_bands", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    ("rt_render_path", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_void_p]),
     ("rt_scatter_gathered", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                       C.c_int, C.c_void_p, C.c_void_p]),
     ("rt_wire_layout_of", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(rt_wire_layout)]),
