@@ -1,6 +1,9 @@
 """Static instruction mix of one kernel in an assembly listing (make -C csrc asm).
 
-    python tools/isa_mix.py uu-infogr-raytracer_amd/csrc/obj/rt_kernel.s trace_direct_kernelILi1ELb0ELb0ELi0 [N]
+    python tools/isa_mix.py uu-infogr-raytracer_amd/csrc/obj/rt_kernel.s trace_direct_kernelILi1ELj6144EE [N]
+
+The key is a piece of the mangled name: trace_{direct,bundle}_kernel[_gpow]<K, V> is ...kernelILi<K>ELj<V>EE, V
+the variant word in decimal (rt_internal.h variant_word; 6144 = vf_cls(8) | vf_wpg(1): C2's batch kernel).
 """
 import collections
 import sys

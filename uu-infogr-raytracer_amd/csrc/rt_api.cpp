@@ -912,6 +912,29 @@ struct EncTarget {
     int tiles_x, tpf, frame0;
 };
 
+// The tail of trace_bands and trace_path: lp launched on `stream` as one of device d's sampled-timing traces
+// (`what` names the caller in the error text), the launch counted and, while the context counts
+// (rt_set_counting), the pixels of rows < H in the nb launched bands (first, step) of n_frames frames; ss:
+// supersampling, so samples.  Nothing but the launch lies between the timing events; a caller that probes the
+// dispatch order brackets the whole call with order_begin / order_end.
+int launch_counted(rt_ctx* ctx, Device& d, hipStream_t stream, const LaunchParams& lp, const char* what, int W, int H,
+                   int band_rows, int first, int step, int nb, int n_frames, int ss) {
+    hipStream_t saved = d.stream;
+    d.stream = stream;
+    const bool timed = begin_timed(ctx, d, 0);
+    const int e = launch_trace(lp, ctx->layout.generic_pow, false, stream);
+    end_timed(d, timed);
+    d.stream = saved;
+    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString((hipError_t)e));
+    ctx->launches++;
+    for (int k = 0; k < nb && ctx->counting; ++k) {
+        const long long y0 = (long long)(first + k * step) * band_rows;
+        ctx->prim_rays += ((uint64_t)std::min<long long>(band_rows, (long long)H - y0) * (uint64_t)W * (uint64_t)n_frames)
+                          << (2 * ss);
+    }
+    return RT_OK;
+}
+
 // Launch the trace of bands (first, step) of `band_rows` rows (at most max_bands of them) into `out` on
 // device d.  `slice`: a Tick hand-off (CopyJob) that rides in the launch as its copy slice.
 // Supersampling (rt_set_supersampling, k = 1 << ss > 1): the arguments are in output pixels as ever, and so
@@ -953,8 +976,7 @@ int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, int ba
     const bool lone = n_frames <= 1 && whole && lp.S < CULL_MIN_SPHERES && lp.row_order_n == (H + 7) / 8;
     // the bundle kernel's all-lights-ok merged instantiation (C4/C5): natural or measured tile order
     const SceneLayout& L = ctx->layout;
-    const bool lone_bundle = n_frames <= 1 && whole && lp.S >= CULL_MIN_SPHERES && lp.S <= 64 && lp.L >= 1 &&
-                             lp.L <= SHADOW_MERGE_L && L.lights_a2_ok && !L.generic_pow;
+    const bool lone_bundle = n_frames <= 1 && whole && merged_class(lp.S, lp.L, L.lights_a2_ok) == 2 && !L.generic_pow;
     bool probe = false;
     int cand = -1;
     if (lone || lone_bundle) {
@@ -982,22 +1004,10 @@ int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, int ba
         lp.copy_z = 1;
         lp.out_frame_bytes = 0;
     }
-    hipStream_t saved = d.stream;
-    d.stream = stream;
-    const bool timed = begin_timed(ctx, d, 0);
     probe = probe && order_begin(d, cand, stream);
-    int e = launch_trace(lp, ctx->layout.generic_pow, false, stream);
+    rc = launch_counted(ctx, d, stream, lp, "trace", W, H, band_rows, first, step, nb, n_frames, ss);
     if (probe) order_end(d, stream);
-    end_timed(d, timed);
-    d.stream = saved;
-    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "trace launch failed: %s", hipGetErrorString((hipError_t)e));
-    ctx->launches++;
-    for (int k = 0; k < nb && ctx->counting; ++k) {  // pixels of rows < H in the launched bands (counted launches)
-        const long long y0 = (long long)(first + k * step) * band_rows;
-        ctx->prim_rays += ((uint64_t)std::min<long long>(band_rows, (long long)H - y0) * (uint64_t)W * (uint64_t)n_frames)
-                          << (2 * ss);  // (supersampling: samples)
-    }
-    return RT_OK;
+    return rc;
 }
 
 // `sampled`: a render that supersamples (its k W x k H sample frame is bounded like any frame).
@@ -1596,11 +1606,10 @@ int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_
     L.off_cull = al(L.off_li + sizeof(DevLight) * (size_t)n_lights);
     L.off_shcull = al(L.off_cull + sizeof(DevSphereCull) * (size_t)n_spheres);
     L.has_shcull = (long long)n_lights * (long long)n_spheres <= SHADOW_CULL_MAX_ENTRIES;
-    // shadow grids: the bundle kernel's merged pass only (CULL_MIN_SPHERES <= S <= 64, 1 <= L <=
-    // SHADOW_MERGE_L); RT_SHADOW_GRID=0 keeps the per-level bound (A/B and fallback tests)
+    // shadow grids: the bundle kernel's merged pass only (merged_class 1 or 2, whatever the lights' 2a);
+    // RT_SHADOW_GRID=0 keeps the per-level bound (A/B and fallback tests)
     const char* gv = std::getenv("RT_SHADOW_GRID");
-    L.has_shg = n_spheres >= CULL_MIN_SPHERES && n_spheres <= 64 && n_lights >= 1 && n_lights <= SHADOW_MERGE_L &&
-                !(gv && std::strcmp(gv, "0") == 0);
+    L.has_shg = merged_class(n_spheres, n_lights, true) != 0 && !(gv && std::strcmp(gv, "0") == 0);
     L.off_shg = al(L.off_shcull + (L.has_shcull ? sizeof(DevShadowCull) * (size_t)n_lights * (size_t)n_spheres : 0));
     L.off_shgrid = al(L.off_shg + (L.has_shg ? sizeof(DevShadowGrid) * (size_t)n_lights : 0));
     L.off_shslab = al(L.off_shgrid + (L.has_shg ? sizeof(unsigned long long) * SHGRID_N * SHGRID_N * (size_t)n_lights : 0));
@@ -2375,20 +2384,10 @@ int trace_path(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const r
     lp.out_fmt = fmt;
     lp.n_frames = n_frames;
     lp.out_frame_bytes = frame_bytes;
-    hipStream_t saved = d.stream;
-    d.stream = stream;
-    const bool timed = begin_timed(ctx, d, 0);
-    const int e = launch_trace(lp, ctx->layout.generic_pow, false, stream);
-    end_timed(d, timed);
-    d.stream = saved;
-    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "path launch failed: %s", hipGetErrorString((hipError_t)e));
+    rc = launch_counted(ctx, d, stream, lp, "path", W, H, band_rows, first, step, nb, n_frames, 0);
+    if (rc != RT_OK) return rc;
     HIP_TRY(ctx, hipEventRecord(ps.done, stream));
     ps.busy = true;
-    ctx->launches++;
-    for (int k = 0; k < nb && ctx->counting; ++k) {  // pixels of rows < H in the launched bands (counted launches)
-        const long long y0 = (long long)(first + k * step) * band_rows;
-        ctx->prim_rays += (uint64_t)std::min<long long>(band_rows, (long long)H - y0) * (uint64_t)W * (uint64_t)n_frames;
-    }
     return RT_OK;
 }
 

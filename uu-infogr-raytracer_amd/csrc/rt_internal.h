@@ -261,6 +261,103 @@ constexpr int SINGLE_WPG = 4;
 // The kernel argument block: raising ROW_ORDER_MAX or MAX_PRIM_CONST must not push it past 4 KiB.
 static_assert(sizeof(LaunchParams) < 4096, "LaunchParams is passed by value as the kernarg block (< 4 KiB)");
 
+constexpr int OUT_TILES = 3;
+
+// ---------------------------------------------------------------------------------
+// Trace kernel variants.  A trace launch runs one instantiation of one of four entry points
+// (rt_kernel.hip trace_{direct,bundle}_kernel[_gpow]<K, V>); which one is decided here, on the host, from the
+// launch parameters alone, and described by a TraceVariant.  Its fields but K travel to the kernels as one
+// word V of named options (variant_word), which every level of the kernel code reads by name.
+// ---------------------------------------------------------------------------------
+// Scenes with at most DIRECT_SMAX spheres (every BASELINE config of the direct kernel) run a
+// direct kernel whose sphere-pair loops are unrolled.
+constexpr int DIRECT_SMAX = 8;
+
+enum : int { TV_DIRECT = 0, TV_BUNDLE = 1 };
+// PLAIN: pixels to `out`.  STATS: as PLAIN, and the diagnostic tallies of the executed work.  TILES: out_fmt
+// OUT_TILES, the fused tile encoder.  SS: the supersampling epilogue.  PATH: one DevView per grid z.
+enum : int { TM_PLAIN = 0, TM_STATS = 1, TM_TILES = 2, TM_SS = 3, TM_PATH = 4 };
+struct TraceVariant {
+    int family;  // TV_*
+    int gpow;    // some material needs the f64 Math.Pow path: the entry points without the register caps
+    int mode;    // TM_*
+    int cls;     // direct: SMAX, the compile-time sphere bound (DIRECT_SMAX or 0 = none); bundle: MERGED 0, 1 or 2
+    int K;       // stack records: limit + 1 rounded up to 1, 2, 4, 6, 8, or 64 (the scratch stack)
+    int wpg;     // tiles (waves) per workgroup: 1, or SINGLE_WPG for a lone frame on the direct kernel
+    int tord;    // 0: tiles in grid order (row_order / col_major), 1: tile_order, 2: as 0 and tile_cost recorded
+};
+
+enum : unsigned { VF_GPOW = 1u, VF_STATS = 2u, VF_TILES = 4u, VF_SS = 8u, VF_PATH = 16u };
+constexpr unsigned vf_cls(int c) { return (unsigned)c << 8; }
+constexpr unsigned vf_wpg(int w) { return (unsigned)w << 12; }
+constexpr unsigned vf_tord(int t) { return (unsigned)t << 16; }
+constexpr int vf_cls_of(unsigned v) { return (int)(v >> 8 & 15u); }  // SMAX (direct) / MERGED (bundle)
+constexpr int vf_wpg_of(unsigned v) { return (int)(v >> 12 & 15u); }
+constexpr int vf_tord_of(unsigned v) { return (int)(v >> 16 & 3u); }
+static_assert(DIRECT_SMAX < 16 && SINGLE_WPG < 16, "the variant word's 4-bit fields");
+constexpr unsigned variant_word(const TraceVariant& v) {
+    return (v.gpow ? VF_GPOW : 0u) | (v.mode == TM_STATS ? VF_STATS : 0u) | (v.mode == TM_TILES ? VF_TILES : 0u) |
+           (v.mode == TM_SS ? VF_SS : 0u) | (v.mode == TM_PATH ? VF_PATH : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) |
+           vf_tord(v.tord);
+}
+
+// The bundle family's shadow pass by scene: 0 = per light (also every scene of the direct family), 1 = the
+// merged pass for S <= 64 spheres and 1..SHADOW_MERGE_L lights (the scenes with shadow grids), 2 = the merged
+// pass with every light's 2a finite and > 0 (the exact-threshold form).
+inline int merged_class(int S, int L, bool lights_a2_ok) {
+    if (S < CULL_MIN_SPHERES || !(S <= 64 && L >= 1 && L <= SHADOW_MERGE_L)) return 0;
+    return lights_a2_ok ? 2 : 1;
+}
+
+// The instantiations that exist (384): every mode, depth and class of both families at one tile per workgroup
+// in grid order; the direct kernel's lone-frame workgroups of SINGLE_WPG tiles in each tile order (PLAIN
+// only); the all-lights-ok merged bundle kernel's tile orders (PLAIN, no GPOW).
+constexpr bool trace_variant_built(const TraceVariant& v) {
+    const bool plain = v.mode == TM_PLAIN;
+    if (v.family == TV_DIRECT)
+        return (v.cls == 0 || v.cls == DIRECT_SMAX) && (v.wpg == 1 ? v.tord == 0 : v.wpg == SINGLE_WPG && plain);
+    return v.cls >= 0 && v.cls <= 2 && v.wpg == 1 && (v.tord == 0 || (plain && !v.gpow && v.cls == 2));
+}
+
+// The variant a launch of p runs; false: a combination no kernel is built for (launch_trace answers
+// hipErrorInvalidValue; rt_api.cpp refuses these before any launch).  No device call.
+inline bool pick_trace_variant(const LaunchParams& p, bool generic_pow, bool stats, TraceVariant* v) {
+    const bool tiles = p.out_fmt == OUT_TILES, ordered = p.tile_order != nullptr || p.tile_cost != nullptr;
+    if (p.views != nullptr) {
+        if (p.ss_log2 > 0 || tiles || stats || ordered || p.copy_z != 0 || p.row_order_n != 0 || p.col_major != 0)
+            return false;
+        v->mode = TM_PATH;
+    } else if (p.ss_log2 > 0) {
+        if (p.ss_log2 > 3 || tiles || stats || ordered) return false;
+        v->mode = TM_SS;
+    } else {
+        v->mode = tiles ? TM_TILES : stats ? TM_STATS : TM_PLAIN;  // (the fused encoder never tallies)
+    }
+    v->gpow = generic_pow;
+    // Instantiation per recursion depth: K = limit + 1 records (levels 0..limit each push at most
+    // one), rounded up to the LDS stack sizes; deeper limits use the scratch stack.
+    const int need = p.limit + 1;
+    v->K = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 6 ? 6 : need <= 8 ? 8 : 64;
+    const int tord = v->mode != TM_PLAIN ? 0 : p.tile_cost != nullptr ? 2 : p.tile_order != nullptr ? 1 : 0;
+    // bundle culling pays for its per-wave bounds only with enough spheres (A/B: +15 % at
+    // 8 spheres, 3x faster at 64)
+    if (p.S >= CULL_MIN_SPHERES) {
+        v->family = TV_BUNDLE;
+        v->cls = merged_class(p.S, p.L, p.lights_a2_ok != 0);
+        v->wpg = 1;
+        // the all-lights-ok merged instantiation's single-frame tile orders (no GPOW); the others keep grid order
+        v->tord = v->cls == 2 && !generic_pow ? tord : 0;
+    } else {
+        v->family = TV_DIRECT;
+        v->cls = p.S <= DIRECT_SMAX ? DIRECT_SMAX : 0;
+        // a lone frame: SINGLE_WPG tiles of a tile row per workgroup, in the order the host picked
+        const bool lone = SINGLE_WPG > 1 && v->mode == TM_PLAIN && p.n_frames <= 1 && p.copy_z == 0;
+        v->wpg = lone ? SINGLE_WPG : 1;
+        v->tord = lone ? tord : 0;
+    }
+    return true;
+}
+
 // Debug-view segment (layout of rt_segment in include/raytracer_hip.h).
 struct DevSegment {
     float ox, oy, oz, ex, ey, ez;
@@ -281,8 +378,6 @@ int launch_scatter_bands(const int32_t* bands, int32_t* frame, int W, int H, int
 // A CopyJob on its own (the Tick hand-off when no later trace launch carries it: the last chunk of a
 // synchronous rt_render, rt_wait's flush of rt_render_async's last frame).
 int launch_band_copy(const CopyJob& job, void* stream);
-
-constexpr int OUT_TILES = 3;
 
 // Band-set tile codec (rt_codec.hip; format: raytracer_hip/tilecodec.py).
 struct CodecGeom {
