@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/raytracer_hip.h"
+#include "rt_dark.h"
 #include "rt_internal.h"
 
 using namespace rtk;
@@ -1688,6 +1689,12 @@ int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_
         li[i] = d;
         for (int k = 0; k < 3; ++k) frames[(size_t)i].U[k] = U[k], frames[(size_t)i].V[k] = V[k], frames[(size_t)i].A[k] = A[k];
     }
+    // the dark-tile skip (rt_dark.h): planes whose material and the scene's lights pass the host part of its guard;
+    // RT_DARK_SKIP=0 leaves the bit clear (A/B)
+    const char* dv = std::getenv("RT_DARK_SKIP");
+    if (!(dv && std::strcmp(dv, "0") == 0))
+        for (int i = 0; i < n_planes; ++i)
+            if (plane_dark_ok(pl[i], mat[n_spheres + i], li, n_lights)) mat[n_spheres + i].flags |= MAT_DARK_OK;
     if (L.has_shg)
         for (int j = 0; j < n_lights; ++j)
             build_shadow_grid(li[j], frames[(size_t)j], sph, cull, n_spheres, ((DevShadowGrid*)(blob.data() + L.off_shg))[j],

@@ -20,7 +20,8 @@ struct DevSphere {
     float cx, cy, cz, r2;
 };
 
-enum : uint32_t { MAT_MIRROR = 1u, MAT_DIFFUSE = 2u, MAT_SPEC = 4u };
+// MAT_DARK_OK (plane materials): the host part of the dark-tile skip's guard holds (rt_dark.h plane_dark_ok)
+enum : uint32_t { MAT_MIRROR = 1u, MAT_DIFFUSE = 2u, MAT_SPEC = 4u, MAT_DARK_OK = 8u };
 
 enum : uint32_t { POW_GENERIC = 0u, POW_ONE = 1u, POW_HALF = 2u, POW_TWO = 3u };
 
