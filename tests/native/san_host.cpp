@@ -10,7 +10,8 @@
 //     :892-896, primary-segment constants, conservative screen boxes in double) over random
 //     and degenerate cameras, cross-checked bit for bit against the oracle's camera view;
 //   * OnKeyPress / OnMouseMove (:543-554, :1058-1061), rt_write_ppm, rt_wire_layout_of,
-//     and the argument checks of every entry point (no device call is reached).
+//     and the argument checks of every entry point (no device call is reached);
+//   * the Tick hand-off's band plan and copy jobs (for_band_copies, share_job): every frame word once.
 // Exit status 0 = all checks passed; any sanitizer report aborts the process.
 #include "../../uu-infogr-raytracer_amd/csrc/rt_api.cpp"
 
@@ -661,6 +662,58 @@ void check_row_order() {
     }
 }
 
+// The Tick hand-off's band plan (for_band_copies) and copy jobs (share_job): for every frame size, worker count,
+// chunk count and pinned / unpinned frame, the copies of every worker's share, chunk by chunk, write every word
+// of the frame exactly once, read no word of a worker's packed band set twice and none outside it; so do the
+// copy jobs, under the copy kernel's rule for where word i of a job lands.
+void check_band_plans() {
+    const int sizes[][2] = {{643, 357}, {100, 9}, {37, 1}, {1, 61}, {250, 131}, {8, 8}, {5, 17}};
+    long plans = 0;
+    for (const auto& size : sizes)
+        for (int n = 1; n <= 8; ++n)
+            for (int nc = 1; nc <= 8; ++nc)
+                for (int pinned = 0; pinned < 2; ++pinned, ++plans) {
+                    const int W = size[0], H = size[1];
+                    std::vector<int> frame((size_t)W * H, 0), jframe((size_t)W * H, 0);
+                    size_t outside = 0, reread = 0, miswritten = 0;
+                    for (int g = 0; g < n; ++g) {
+                        const Share sh = share_of(W, H, g, n, nc > 1);
+                        const size_t packed = (size_t)std::max(sh.nb, 0) * sh.band_rows * W;
+                        std::vector<int> read(packed, 0);
+                        for (int c = 0; c < nc; ++c) {
+                            const Bands b = chunk_bands(sh, c, nc);
+                            const int rc = for_band_copies(
+                                sh, W, H, b.k0, b.k1, pinned != 0,
+                                [&](size_t dst, size_t src, size_t width, size_t rows, size_t pitch) {
+                                    for (size_t r = 0; r < rows; ++r)
+                                        for (size_t i = 0; i < width; ++i) {
+                                            const size_t to = dst + r * pitch + i, from = src + r * width + i;
+                                            if (to < frame.size() && from < packed) ++frame[to], ++read[from];
+                                            else ++outside;
+                                        }
+                                    return (int)RT_OK;
+                                });
+                            CHECK(rc == RT_OK, "for_band_copies rc %d", rc);
+                            if (b.k1 <= b.k0) continue;
+                            const CopyJob j = share_job(sh, W, H, b.k0, b.k1, nullptr, jframe.data());
+                            for (size_t i = 0; i < j.words; ++i) {  // (the copy kernel's rule, rt_kernel.hip band_dst)
+                                const size_t at = j.band_words == 0 ? i : (i / j.band_words) * j.dst_stride + i % j.band_words;
+                                const size_t to = (size_t)(j.dst - jframe.data()) + at;
+                                if (to < jframe.size()) ++jframe[to];
+                                else ++outside;
+                            }
+                        }
+                        for (int r : read) reread += r > 1;
+                    }
+                    for (size_t i = 0; i < frame.size(); ++i) miswritten += (frame[i] != 1) + (jframe[i] != 1);
+                    CHECK(outside == 0 && reread == 0 && miswritten == 0,
+                          "%dx%d, %d workers, %d chunks, pinned %d: %zu words outside the frame or the band set, %zu source "
+                          "words read twice, %zu frame words not written exactly once (plan + jobs)",
+                          W, H, n, nc, pinned, outside, reread, miswritten);
+                }
+    std::printf("band_plans: %ld plans\n", plans);
+}
+
 void check_library() {
     CHECK(rt_abi_version() == RT_ABI_VERSION, "ABI version");
     int n = -1;
@@ -774,6 +827,7 @@ int main() {
     check_ball_cull();
     check_cluster_cull();
     check_row_order();
+    check_band_plans();
     std::printf("san_host: %d failures\n", failures);
     return failures ? 1 : 0;
 }

@@ -187,14 +187,17 @@ def test_tick_ragged_vs_oracle(oracle, chunks_env, size, world, registered):
             check_guard(buf)
 
 
-@pytest.mark.parametrize("mode", [None, "slice", "stream"])
+@pytest.mark.parametrize("mode,chunks", [(None, None), ("slice", None), ("stream", None), ("stream", 3)],
+                         ids=["None", "slice", "stream", "stream-chunks3"])
 @pytest.mark.parametrize("world", [1, 2, 4, 7])
-def test_tick_async_workers_vs_oracle(oracle, async_env, world, mode):
+def test_tick_async_workers_vs_oracle(oracle, async_env, chunks_env, world, mode, chunks):
     """rt_render_async at n workers: 7 frames queued, a new camera each and the frame size changing twice
     mid-queue, each into its own registered buffer, ONE rt_wait -- every frame = the oracle's.  Every
     worker double-buffers its band set on its own stream; frame k's copy rides in frame k+1's launch (slice)
-    or runs on the copy engine behind frame k's trace (stream; the default for large shares)."""
+    or runs on the copy engine behind frame k's trace (stream; the default for large shares), there also in
+    three chunks per share (RT_TICK_CHUNKS=3: each chunk's copy behind its own trace)."""
     async_env(mode)
+    chunks_env(chunks)
     base = scenes.config("C3")
     sizes = [(320, 180)] * 3 + [(200, 113)] * 2 + [(320, 180)] * 2
     rng = np.random.default_rng(7)

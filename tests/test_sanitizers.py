@@ -44,3 +44,5 @@ def test_oracle_tsan_disjoint_rows(built):
 def test_host_api_asan_ubsan(built):
     out = _run([os.path.join(built, "san_host_asan")], {"UBSAN_OPTIONS": "print_stacktrace=1"})
     assert "san_host: 0 failures" in out
+    # the Tick hand-off's band plan: 7 sizes x 8 worker counts x 8 chunk counts x pinned / unpinned
+    assert "band_plans: 896 plans" in out

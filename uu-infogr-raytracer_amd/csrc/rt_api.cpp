@@ -145,16 +145,22 @@ struct Device {
         int32_t* host = nullptr;  // caller's buffer (one contiguous band set: hipMemcpyAsync on a flush)
         CopyJob job{};            // the band set -> the buffer's device-mapped address (job.words 0: none)
     } hand;
-    hipEvent_t ev_join = nullptr;  // rt_render_device at n > 1: ordering against the caller's stream
-    // the synchronous Tick's copy-engine hand-off of chunk c on its own stream, after the chunk's trace
+    // the copy-engine hand-off of chunk c (trace_and_copy_chunks) on its own stream, after the chunk's trace
     hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_chunk[8] = {};
-    // rt_render_async's copy-engine hand-off (RT_TICK_ASYNC=stream): slot s traced -> copied events
-    hipEvent_t ev_traced[2] = {}, ev_copied[2] = {};
-    bool copy_pending[2] = {false, false};
-    // frames in flight of the copy-engine hand-off (rt_ctx::tick_inflight): frame f's copy done -> ring[f % 16]
+    bool copy_pending[2] = {false, false};  // rt_render_async, RT_TICK_ASYNC=stream: slot s has a copy queued
     static constexpr int RING = 16;
-    hipEvent_t ev_ring[RING] = {};
+    // The worker's plain events, made on first use (ensure_event) and destroyed in one loop by rt_destroy.
+    enum Ev {
+        EV_JOIN,                              // rt_render_device at n > 1: ordering against the caller's stream
+        EV_CHUNK,                             // [8] chunk c of a copy-engine hand-off traced
+        EV_COPIED = EV_CHUNK + 8,             // [2] rt_render_async's copy-engine hand-off: slot s copied
+        EV_RING = EV_COPIED + 2,              // [RING] frames in flight of that hand-off (rt_ctx::tick_inflight):
+                                              // frame f's copy done -> EV_RING + f % RING
+        EV_PATH_TRACED = EV_RING + RING,      // [2] rt_render_path: d_path[b] traced,
+        EV_PATH_COPIED = EV_PATH_TRACED + 2,  // [2] copied
+        EV_COUNT = EV_PATH_COPIED + 2
+    };
+    hipEvent_t ev[EV_COUNT] = {};
     uint64_t frames_issued = 0;
     // Camera-path launches (rt_render_path_bands): the frames' DevView records go through a ring of table slots
     // -- pinned staging, hipMemcpyAsync on the caller's stream ahead of the launch, an event after it; a slot is
@@ -174,7 +180,6 @@ struct Device {
     // (copy_stream) under the trace of chunk c + 1
     int32_t* d_path[2] = {nullptr, nullptr};
     size_t path_cap[2] = {0, 0};
-    hipEvent_t ev_path_traced[2] = {}, ev_path_copied[2] = {};
     float* d_view_tab = nullptr;  // lx[W] then ly[H] (view_tables)
     size_t view_tab_cap = 0;
     int tab_w = -1, tab_h = -1;
@@ -297,6 +302,12 @@ static int fail(rt_ctx* ctx, int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail((ctx), RT_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
+#define RT_TRY(call)                     \
+    do {                                 \
+        const int rc_ = (call);          \
+        if (rc_ != RT_OK) return rc_;    \
+    } while (0)
+
 namespace {
 struct DeviceGuard {
     int prev = -1;
@@ -318,6 +329,16 @@ int grow(rt_ctx* ctx, void** p, size_t* cap, size_t bytes) {
     hipError_t e = hipMalloc(p, bytes);
     if (e != hipSuccess) return fail(ctx, RT_ERR_OOM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
     *cap = bytes;
+    return RT_OK;
+}
+
+// A lazily made handle on the current device: an ordering-only event, a non-blocking stream.
+int ensure_event(rt_ctx* ctx, hipEvent_t* ev) {
+    if (!*ev) HIP_TRY(ctx, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    return RT_OK;
+}
+int ensure_stream(rt_ctx* ctx, hipStream_t* s) {
+    if (!*s) HIP_TRY(ctx, hipStreamCreateWithFlags(s, hipStreamNonBlocking));
     return RT_OK;
 }
 
@@ -421,6 +442,10 @@ int total_bands(int H, int band_rows) { return (H + band_rows - 1) / band_rows; 
 int bands_of(int H, int band_rows, int first, int step) {
     int tb = total_bands(H, band_rows);
     return first < tb ? (tb - 1 - first) / step + 1 : 0;
+}
+// Bytes of one frame's output of a band render in `fmt`.
+size_t band_output_bytes(int W, int H, int nb, int band_rows, int fmt) {
+    return fmt == RT_BANDS_FRAME ? (size_t)W * H * 4 : (size_t)nb * band_rows * W * (fmt == RT_BANDS_RGB24 ? 3 : 4);
 }
 
 // Conservative screen box of a sphere for primary rays (culling only; computed in double).
@@ -936,26 +961,35 @@ int launch_counted(rt_ctx* ctx, Device& d, hipStream_t stream, const LaunchParam
     return RT_OK;
 }
 
-// Launch the trace of bands (first, step) of `band_rows` rows (at most max_bands of them) into `out` on
-// device d.  `slice`: a Tick hand-off (CopyJob) that rides in the launch as its copy slice.
-// Supersampling (rt_set_supersampling, k = 1 << ss > 1): the arguments are in output pixels as ever, and so
+// A trace_bands launch: bands (first, step) of `band_rows` rows of the W x H frame, at most max_bands of them
+// (bands_of: how many there are), into `out`.
+struct TraceReq {
+    int W, H, band_rows, first, step;
+    int32_t* out;
+    int fmt = RT_BANDS_INT32;
+    int n_frames = 1;                 // frames of the launch (grid z), frame_bytes apart in `out`
+    size_t frame_bytes = 0;
+    const EncTarget* enc = nullptr;   // the fused tile encoder's target
+    const CopyJob* slice = nullptr;   // a Tick hand-off that rides in the launch as its copy slice
+    int max_bands = INT_MAX;
+};
+
+// Launch the trace `q` on device d.
+// Supersampling (rt_set_supersampling, k = 1 << ss > 1): the request is in output pixels as ever, and so
 // is everything the callers do with the output (band sets, hand-offs, gathers); the launch itself works on
 // the k W x k H sample frame -- the same bands, each k times as many sample rows -- and its epilogue writes
 // one output pixel per k x k block (LaunchParams::ss_log2).  check_ctx bounds k W * k H.
-int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, int band_rows, int first, int step,
-                int32_t* out, int* n_bands, int fmt = RT_BANDS_INT32, int n_frames = 1, size_t frame_bytes = 0,
-                const EncTarget* enc = nullptr, const CopyJob* slice = nullptr, int max_bands = INT_MAX) {
+int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, const TraceReq& q) {
+    const int W = q.W, H = q.H, band_rows = q.band_rows, first = q.first, step = q.step, n_frames = q.n_frames;
+    const EncTarget* enc = q.enc;
     const int ss = ctx->ss_log2;
     if (ss > 0 && enc) return fail(ctx, RT_ERR_UNSUPPORTED, "the fused tile encoder does not supersample");
     LaunchParams lp;
     std::memset(&lp, 0, sizeof lp);
-    int rc = view_params(ctx, W << ss, H << ss, lp, ss);
-    if (rc != RT_OK) return rc;
+    RT_TRY(view_params(ctx, W << ss, H << ss, lp, ss));
     scene_params(ctx, d, lp);
-    rc = view_tables(ctx, d, lp, ss);
-    if (rc != RT_OK) return rc;
-    const int nb = std::min(bands_of(H, band_rows, first, step), max_bands);
-    if (n_bands) *n_bands = nb;
+    RT_TRY(view_tables(ctx, d, lp, ss));
+    const int nb = std::min(bands_of(H, band_rows, first, step), q.max_bands);
     lp.band_first = first, lp.band_step = step;
     if (ss > 0) {
         // (a band of H rows or more is the frame as band 0 whatever its size: k band_rows stays below k H)
@@ -966,12 +1000,12 @@ int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, int ba
         lp.band_rows = band_rows;
         lp.local_rows = nb * band_rows;
     }
-    lp.out = out;
-    lp.out_fmt = fmt;
+    lp.out = q.out;
+    lp.out_fmt = q.fmt;
     lp.n_frames = n_frames;
-    lp.out_frame_bytes = frame_bytes;
+    lp.out_frame_bytes = q.frame_bytes;
     // single-frame launches of a whole frame on the direct kernel: the dispatch order (order_pick)
-    const bool with_copy = slice && slice->words;
+    const bool with_copy = q.slice && q.slice->words;
     // (supersampling launches are never lone: natural tile order, one tile per workgroup)
     const bool whole = ss == 0 && !enc && !with_copy && band_rows >= lp.local_rows && lp.local_rows == H;
     const bool lone = n_frames <= 1 && whole && lp.S < CULL_MIN_SPHERES && lp.row_order_n == (H + 7) / 8;
@@ -1001,12 +1035,12 @@ int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, int ba
         lp.enc_tiles_x = enc->tiles_x, lp.enc_tpf = enc->tpf, lp.enc_frame0 = enc->frame0;
     }
     if (with_copy) {  // the previous frame's (chunk's) hand-off rides along
-        lp.copy = *slice;
+        lp.copy = *q.slice;
         lp.copy_z = 1;
         lp.out_frame_bytes = 0;
     }
     probe = probe && order_begin(d, cand, stream);
-    rc = launch_counted(ctx, d, stream, lp, "trace", W, H, band_rows, first, step, nb, n_frames, ss);
+    const int rc = launch_counted(ctx, d, stream, lp, "trace", W, H, band_rows, first, step, nb, n_frames, ss);
     if (probe) order_end(d, stream);
     return rc;
 }
@@ -1020,6 +1054,15 @@ int check_ctx(rt_ctx* ctx, int W, int H, bool sampled = true) {
     if (sampled && ctx->ss_log2 > 0 && (((long long)W << ctx->ss_log2) * ((long long)H << ctx->ss_log2)) > (1LL << 31) - 1)
         return fail(ctx, RT_ERR_INVALID_ARG, "frame size %dx%d at supersampling factor %d exceeds 2^31 - 1 samples", W, H,
                     1 << ctx->ss_log2);
+    return RT_OK;
+}
+
+// The band arguments of the band renders (`who` names the entry point in the error text).
+int check_band_args(rt_ctx* ctx, const char* who, int band_rows, int band_first, int band_step, const void* d_out,
+                    int format) {
+    if (band_rows <= 0 || band_first < 0 || band_step <= 0 || !d_out ||
+        (format != RT_BANDS_INT32 && format != RT_BANDS_RGB24 && format != RT_BANDS_FRAME))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: bad band arguments", who);
     return RT_OK;
 }
 
@@ -1065,17 +1108,57 @@ Share share_of(int W, int H, int g, int n, bool banded) {
     sh.words = share_words(sh, W, H, 0, sh.nb);
     return sh;
 }
+// Where band k of a share starts in the frame, in int32.
+size_t band_word0(const Share& sh, int W, int k) {
+    return (size_t)(sh.first + (size_t)k * sh.step) * (size_t)sh.band_rows * (size_t)W;
+}
+// Bands [k0, k1) of chunk c of nc of a share (none when the share has fewer bands than chunks).
+struct Bands {
+    int k0, k1;
+};
+Bands chunk_bands(const Share& sh, int c, int nc) {
+    return Bands{(int)((long long)sh.nb * c / nc), (int)((long long)sh.nb * (c + 1) / nc)};
+}
+// The trace of bands [k0, k1) of a share into the packed band set at buf (band 0); `slice` rides in the launch.
+TraceReq share_req(const Share& sh, int W, int H, int k0, int k1, int32_t* buf, const CopyJob* slice = nullptr) {
+    TraceReq q{W, H, sh.band_rows, sh.first + k0 * sh.step, sh.step, buf + (size_t)k0 * sh.band_rows * W};
+    q.slice = slice;
+    q.max_bands = k1 - k0;
+    return q;
+}
 // The hand-off of bands [k0, k1) of a share, traced at src (packed from band k0), into the frame whose
 // row 0 is at `frame` (a device-mapped host address or device memory of this worker).
 CopyJob share_job(const Share& sh, int W, int H, int k0, int k1, const int32_t* src, int32_t* frame) {
     CopyJob j{};
     const size_t bw = (size_t)sh.band_rows * (size_t)W;
     j.src = src;
-    j.dst = frame + (size_t)(sh.first + (size_t)k0 * sh.step) * bw;
+    j.dst = frame + band_word0(sh, W, k0);
     j.words = share_words(sh, W, H, k0, k1);
     j.band_words = sh.step == 1 ? 0u : (unsigned)bw;  // one worker: the bands are one contiguous run
     j.dst_stride = (unsigned long long)sh.step * bw;
     return j;
+}
+
+// The copies that hand bands [k0, k1) of a share, packed from band 0, to a frame, each as fn(dst, src, width,
+// rows, pitch) in int32: `rows` runs of `width`, packed at src, to dst + r * pitch in the frame (pitch 0: one
+// run, a plain copy).  One contiguous run (one worker), a pitched copy over the whole bands plus the frame's
+// cut last band (a registered, pinned frame: the copy engine writes the rows in place), or one run per band (an
+// unregistered frame -- the slow path; callers register Surface.pixels once -- where a pitched copy would be
+// staged).  fn returns RT_OK to go on.
+template <class Fn>
+int for_band_copies(const Share& sh, int W, int H, int k0, int k1, bool pinned, Fn&& fn) {
+    if (k1 <= k0) return RT_OK;
+    const size_t bw = (size_t)sh.band_rows * (size_t)W;
+    auto run = [&](int k, int n) { return fn(band_word0(sh, W, k), (size_t)k * bw, share_words(sh, W, H, k, k + n), 1, 0); };
+    if (sh.step == 1) return run(k0, k1 - k0);
+    if (pinned) {
+        const bool cut = share_words(sh, W, H, k1 - 1, k1) < bw;
+        const int full = k1 - k0 - (cut ? 1 : 0);
+        if (full > 0) RT_TRY(fn(band_word0(sh, W, k0), (size_t)k0 * bw, bw, (size_t)full, (size_t)sh.step * bw));
+        return cut ? run(k1 - 1, 1) : RT_OK;
+    }
+    for (int k = k0; k < k1; ++k) RT_TRY(run(k, 1));
+    return RT_OK;
 }
 
 // Issue each worker's pending rt_render_async hand-off (the last frame's D2H) on its async stream.
@@ -1097,36 +1180,44 @@ int flush_hand(rt_ctx* ctx) {
     return RT_OK;
 }
 
-// A worker's band set (src, packed) into the host frame by the runtime's copies: one contiguous copy
-// (one worker), a pitched 2-D copy over the whole bands plus the frame's cut last band (a registered,
-// pinned frame: the copy engine writes the rows in place), or one copy per band (an unregistered frame
-// -- the slow path; callers register Surface.pixels once -- where a pitched copy would be staged).
+// rt_render_async frames still pending are completed first (the caller may reuse their buffers).
+int wait_pending_async(rt_ctx* ctx) {
+    for (const Device& d : ctx->dev)
+        if (d.hand.job.words || d.copy_pending[0] || d.copy_pending[1]) return rt_wait(ctx);
+    return RT_OK;
+}
+
+// Bands [k0, k1) of a worker's band set (src, packed from band 0) into the host frame by the runtime's copies.
 int runtime_band_copy(rt_ctx* ctx, const Share& sh, int W, int H, const int32_t* src, int32_t* host, hipStream_t st,
-                      bool pinned = false, int k0 = 0, int k1 = -1) {
-    if (k1 < 0) k1 = sh.nb;  // bands [k0, k1) of the share; src = the packed band set (band 0)
-    if (k1 <= k0) return RT_OK;
-    const size_t bw = (size_t)sh.band_rows * (size_t)W;
-    auto dst = [&](int k) { return host + (size_t)(sh.first + (size_t)k * sh.step) * bw; };
-    if (sh.step == 1) {
-        HIP_TRY(ctx, hipMemcpyAsync(dst(k0), src + (size_t)k0 * bw, share_words(sh, W, H, k0, k1) * sizeof(int32_t),
-                                    hipMemcpyDeviceToHost, st));
-        return RT_OK;
-    }
-    if (pinned) {
-        const bool cut = share_words(sh, W, H, k1 - 1, k1) < bw;
-        const int full = k1 - k0 - (cut ? 1 : 0);
-        if (full > 0)
-            HIP_TRY(ctx, hipMemcpy2DAsync(dst(k0), (size_t)sh.step * bw * sizeof(int32_t), src + (size_t)k0 * bw,
-                                          bw * sizeof(int32_t), bw * sizeof(int32_t), (size_t)full,
+                      bool pinned, int k0, int k1) {
+    return for_band_copies(sh, W, H, k0, k1, pinned, [&](size_t dst, size_t from, size_t width, size_t rows, size_t pitch) {
+        const size_t wb = width * sizeof(int32_t);
+        if (pitch)
+            HIP_TRY(ctx, hipMemcpy2DAsync(host + dst, pitch * sizeof(int32_t), src + from, wb, wb, rows,
                                           hipMemcpyDeviceToHost, st));
-        if (cut)
-            HIP_TRY(ctx, hipMemcpyAsync(dst(k1 - 1), src + (size_t)(k1 - 1) * bw,
-                                        share_words(sh, W, H, k1 - 1, k1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        return RT_OK;
+        else
+            HIP_TRY(ctx, hipMemcpyAsync(host + dst, src + from, wb, hipMemcpyDeviceToHost, st));
+        return (int)RT_OK;
+    });
+}
+
+// The copy-engine hand-off of a share: each non-empty chunk c of nc is traced into buf (the packed band set) on
+// `trace`, and once its event has fired the copy engine moves it into `host` on the worker's copy stream, under
+// the trace of chunk c + 1.  The wait captures the event's record of this call, so a later frame may record the
+// same event while this frame's copy is still queued.
+int trace_and_copy_chunks(rt_ctx* ctx, Device& d, hipStream_t trace, const Share& sh, int W, int H, int nc,
+                          int32_t* buf, int32_t* host, bool pinned) {
+    RT_TRY(ensure_stream(ctx, &d.copy_stream));
+    for (int c = 0; c < nc; ++c) {
+        const Bands b = chunk_bands(sh, c, nc);
+        if (b.k1 <= b.k0) continue;
+        hipEvent_t& ev = d.ev[Device::EV_CHUNK + c];
+        RT_TRY(ensure_event(ctx, &ev));
+        RT_TRY(trace_bands(ctx, d, trace, share_req(sh, W, H, b.k0, b.k1, buf)));
+        HIP_TRY(ctx, hipEventRecord(ev, trace));
+        HIP_TRY(ctx, hipStreamWaitEvent(d.copy_stream, ev, 0));
+        RT_TRY(runtime_band_copy(ctx, sh, W, H, buf, host, d.copy_stream, pinned, b.k0, b.k1));
     }
-    for (int k = k0; k < k1; ++k)
-        HIP_TRY(ctx, hipMemcpyAsync(dst(k), src + (size_t)k * bw, share_words(sh, W, H, k, k + 1) * sizeof(int32_t),
-                                    hipMemcpyDeviceToHost, st));
     return RT_OK;
 }
 
@@ -1165,7 +1256,7 @@ int gather_frame(rt_ctx* ctx, int width, int height, int32_t* dst) {
         DeviceGuard guard(d.id);
         rc = grow(ctx, (void**)&d.d_bands, &d.bands_cap, slot * sizeof(int32_t));
         if (rc == RT_OK && g == 0) rc = grow(ctx, (void**)&d.d_gather, &d.gather_cap, slot * n * sizeof(int32_t));
-        if (rc == RT_OK) rc = trace_bands(ctx, d, d.stream, width, height, band_rows, g, n, d.d_bands, nullptr);
+        if (rc == RT_OK) rc = trace_bands(ctx, d, d.stream, TraceReq{width, height, band_rows, g, n, d.d_bands});
         if (rc != RT_OK) return rc;
     }
     std::vector<char> gtimed((size_t)n, 0);
@@ -1303,25 +1394,15 @@ void rt_destroy(rt_ctx* ctx) {
         for (EventPair& ep : d.pool) (void)hipEventDestroy(ep.a), (void)hipEventDestroy(ep.b);
         for (auto* v : {&d.order.pending, &d.order.pool})
             for (Device::OrderTuner::Probe& pr : *v) (void)hipEventDestroy(pr.a), (void)hipEventDestroy(pr.b);
-        if (d.ev_join) (void)hipEventDestroy(d.ev_join);
-        for (hipEvent_t& ev : d.ev_chunk)
-            if (ev) (void)hipEventDestroy(ev);
-        for (int i = 0; i < 2; ++i) {
-            if (d.ev_traced[i]) (void)hipEventDestroy(d.ev_traced[i]);
-            if (d.ev_copied[i]) (void)hipEventDestroy(d.ev_copied[i]);
-        }
-        for (hipEvent_t& ev : d.ev_ring)
+        for (hipEvent_t ev : d.ev)
             if (ev) (void)hipEventDestroy(ev);
         for (Device::PathSlot& ps : d.path_slot) {
             if (ps.done) (void)hipEventDestroy(ps.done);
             if (ps.h_views) (void)hipHostFree(ps.h_views);
             if (ps.d_views) (void)hipFree(ps.d_views);
         }
-        for (int i = 0; i < 2; ++i) {
-            if (d.ev_path_traced[i]) (void)hipEventDestroy(d.ev_path_traced[i]);
-            if (d.ev_path_copied[i]) (void)hipEventDestroy(d.ev_path_copied[i]);
+        for (int i = 0; i < 2; ++i)
             if (d.d_path[i]) (void)hipFree(d.d_path[i]);
-        }
         if (d.copy_stream) (void)hipStreamDestroy(d.copy_stream);
         if (d.comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(d.comm);
         if (d.d_scene) (void)hipFree(d.d_scene);
@@ -1832,35 +1913,35 @@ int rt_render_device(rt_ctx* ctx, int width, int height, int32_t* d_pixels, void
     hipStream_t s = (hipStream_t)hip_stream;  // NULL = the HIP null stream
     if (ctx->n_gpus == 1 && !ctx->rccl_gather) {
         DeviceGuard guard(d0.id);
-        rc = trace_bands(ctx, d0, s, width, height, height, 0, 1, d_pixels, nullptr);
+        rc = trace_bands(ctx, d0, s, TraceReq{width, height, height, 0, 1, d_pixels});
     } else {
         // n > 1: the workers start after the work already on the caller's stream (d_pixels may be in use)
         // and the caller's stream waits for the whole frame
         for (Device& d : ctx->dev)
-            if (!d.ev_join) {
+            if (!d.ev[Device::EV_JOIN]) {  // (made on its own device)
                 DeviceGuard guard(d.id);
-                HIP_TRY(ctx, hipEventCreateWithFlags(&d.ev_join, hipEventDisableTiming));
+                RT_TRY(ensure_event(ctx, &d.ev[Device::EV_JOIN]));
             }
         {
             DeviceGuard guard(d0.id);
-            HIP_TRY(ctx, hipEventRecord(d0.ev_join, s));
+            HIP_TRY(ctx, hipEventRecord(d0.ev[Device::EV_JOIN], s));
         }
         for (Device& d : ctx->dev) {
             DeviceGuard guard(d.id);
-            HIP_TRY(ctx, hipStreamWaitEvent(d.stream, d0.ev_join, 0));
+            HIP_TRY(ctx, hipStreamWaitEvent(d.stream, d0.ev[Device::EV_JOIN], 0));
         }
         if (ctx->shared_device) {  // one device: every worker writes its bands straight into the frame
             for (int g = 0; g < ctx->n_gpus && rc == RT_OK; ++g)
-                rc = trace_bands(ctx, ctx->dev[(size_t)g], ctx->dev[(size_t)g].stream, width, height, TICK_BAND_ROWS,
-                                 g, ctx->n_gpus, d_pixels, nullptr, RT_BANDS_FRAME);
+                rc = trace_bands(ctx, ctx->dev[(size_t)g], ctx->dev[(size_t)g].stream,
+                                 TraceReq{width, height, TICK_BAND_ROWS, g, ctx->n_gpus, d_pixels, RT_BANDS_FRAME});
         } else {  // the RCCL gather to device 0 over xGMI, reassembled into d_pixels on device 0's stream
             rc = gather_frame(ctx, width, height, d_pixels);
         }
         if (rc != RT_OK) return rc;
         DeviceGuard guard(d0.id);
         for (size_t g = 0; g < (ctx->shared_device ? ctx->dev.size() : 1); ++g) {
-            HIP_TRY(ctx, hipEventRecord(ctx->dev[g].ev_join, ctx->dev[g].stream));
-            HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->dev[g].ev_join, 0));
+            HIP_TRY(ctx, hipEventRecord(ctx->dev[g].ev[Device::EV_JOIN], ctx->dev[g].stream));
+            HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->dev[g].ev[Device::EV_JOIN], 0));
         }
     }
     if (rc == RT_OK) {
@@ -1878,17 +1959,14 @@ int rt_render_bands(rt_ctx* ctx, int width, int height, int band_rows, int band_
 
 int rt_render_bands_ex(rt_ctx* ctx, int width, int height, int band_rows, int band_first, int band_step, void* d_out,
                        int format, void* hip_stream, int* out_n_bands) {
-    int rc = check_ctx(ctx, width, height);
-    if (rc != RT_OK) return rc;
-    if (band_rows <= 0 || band_first < 0 || band_step <= 0 || !d_out ||
-        (format != RT_BANDS_INT32 && format != RT_BANDS_RGB24 && format != RT_BANDS_FRAME))
-        return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_bands: bad band arguments");
+    RT_TRY(check_ctx(ctx, width, height));
+    RT_TRY(check_band_args(ctx, "rt_render_bands", band_rows, band_first, band_step, d_out, format));
     if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_bands needs a single-GPU context");
     Device& d = ctx->dev[0];
     DeviceGuard guard(d.id);
-    hipStream_t s = (hipStream_t)hip_stream;  // NULL = the HIP null stream
-    int nb = 0;
-    rc = trace_bands(ctx, d, s, width, height, band_rows, band_first, band_step, (int32_t*)d_out, &nb, format);
+    const int nb = bands_of(height, band_rows, band_first, band_step);
+    const int rc = trace_bands(ctx, d, (hipStream_t)hip_stream,  // (NULL = the HIP null stream)
+                               TraceReq{width, height, band_rows, band_first, band_step, (int32_t*)d_out, format});
     if (out_n_bands) *out_n_bands = nb;
     if (rc == RT_OK) ctx->pixels += (uint64_t)nb * band_rows * width;
     return rc;
@@ -1897,21 +1975,18 @@ int rt_render_bands_ex(rt_ctx* ctx, int width, int height, int band_rows, int ba
 int rt_render_bands_batch(rt_ctx* ctx, int width, int height, int band_rows, int band_first, int band_step,
                           int n_frames, void* d_out, size_t frame_stride_bytes, int format, void* hip_stream,
                           int* out_n_bands) {
-    int rc = check_ctx(ctx, width, height);
-    if (rc != RT_OK) return rc;
-    if (band_rows <= 0 || band_first < 0 || band_step <= 0 || !d_out || n_frames <= 0 || n_frames > 65535 ||
-        (format != RT_BANDS_INT32 && format != RT_BANDS_RGB24 && format != RT_BANDS_FRAME))
+    RT_TRY(check_ctx(ctx, width, height));
+    RT_TRY(check_band_args(ctx, "rt_render_bands_batch", band_rows, band_first, band_step, d_out, format));
+    if (n_frames <= 0 || n_frames > 65535)
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_bands_batch: bad band arguments");
     if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_bands_batch needs a single-GPU context");
     const int nb = bands_of(height, band_rows, band_first, band_step);
-    const size_t need = format == RT_BANDS_FRAME ? (size_t)width * height * 4
-                                                 : (size_t)nb * band_rows * width * (format == RT_BANDS_RGB24 ? 3 : 4);
-    if (n_frames > 1 && frame_stride_bytes < need)
+    if (n_frames > 1 && frame_stride_bytes < band_output_bytes(width, height, nb, band_rows, format))
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_bands_batch: frame stride smaller than a frame's output");
     Device& d = ctx->dev[0];
     DeviceGuard guard(d.id);
-    rc = trace_bands(ctx, d, (hipStream_t)hip_stream, width, height, band_rows, band_first, band_step, (int32_t*)d_out,
-                     nullptr, format, n_frames, frame_stride_bytes);
+    const TraceReq q{width, height, band_rows, band_first, band_step, (int32_t*)d_out, format, n_frames, frame_stride_bytes};
+    const int rc = trace_bands(ctx, d, (hipStream_t)hip_stream, q);
     if (out_n_bands) *out_n_bands = nb;
     if (rc == RT_OK) ctx->pixels += (uint64_t)nb * band_rows * width * (uint64_t)n_frames;
     return rc;
@@ -2014,8 +2089,7 @@ int rt_encode_bands(rt_ctx* ctx, int width, int height, int band_rows, int rank,
 
 int rt_render_bands_tiles(rt_ctx* ctx, int width, int height, int band_rows, int rank, int world, int frame0,
                           int n_frames, int batch_frames, void* d_wire, void* hip_stream) {
-    int rc = check_ctx(ctx, width, height, false);
-    if (rc != RT_OK) return rc;
+    RT_TRY(check_ctx(ctx, width, height, false));
     if (ctx->ss_log2 > 0)
         return fail(ctx, RT_ERR_UNSUPPORTED, "rt_render_bands_tiles does not supersample (rt_set_supersampling(ctx, 1) first)");
     rtk::CodecGeom g;
@@ -2026,14 +2100,13 @@ int rt_render_bands_tiles(rt_ctx* ctx, int width, int height, int band_rows, int
     if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_bands_tiles needs a single-GPU context");
     Device& d = ctx->dev[0];
     DeviceGuard guard(d.id);
-    rc = ensure_stage(ctx, d, g);
-    if (rc != RT_OK) return rc;
+    RT_TRY(ensure_stage(ctx, d, g));
     const EncTarget enc{(unsigned char*)d_wire, (uint32_t*)d.d_stage, g.tiles_x, g.tiles_per_frame, frame0};
-    int nb = 0;
-    rc = trace_bands(ctx, d, (hipStream_t)hip_stream, width, height, band_rows, rank, world, (int32_t*)d_wire, &nb,
-                     RT_BANDS_INT32, n_frames, 0, &enc);
+    TraceReq q{width, height, band_rows, rank, world, (int32_t*)d_wire};
+    q.n_frames = n_frames, q.enc = &enc;
+    const int rc = trace_bands(ctx, d, (hipStream_t)hip_stream, q);
     if (rc == RT_OK) {
-        ctx->pixels += (uint64_t)nb * band_rows * width * (uint64_t)n_frames;
+        ctx->pixels += (uint64_t)bands_of(height, band_rows, rank, world) * band_rows * width * (uint64_t)n_frames;
         if (frame0 == 0 || !d.staged.valid || d.staged.wire != d_wire)
             d.staged = {true, width, height, band_rows, rank, world, batch_frames, d_wire};
     }
@@ -2246,43 +2319,26 @@ int tick_sync(rt_ctx* ctx, int W, int H, int32_t* pixels) {
         const int nc = mode != TICK_RUNTIME ? chunks : 1;
         const Share sh = share_of(W, H, g, n, nc > 1);
         if (sh.nb <= 0) continue;
-        int rc = grow(ctx, (void**)&d.d_bands, &d.bands_cap, (size_t)sh.nb * sh.band_rows * W * sizeof(int32_t));
-        if (rc != RT_OK) return rc;
+        RT_TRY(grow(ctx, (void**)&d.d_bands, &d.bands_cap, (size_t)sh.nb * sh.band_rows * W * sizeof(int32_t)));
         if (mode == TICK_STREAM && nc > 1) {  // chunk c: trace (stream) -> event -> copy engine (copy stream)
-            if (!d.copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking));
-            for (int c = 0; c < nc; ++c) {
-                const int k0 = (int)((long long)sh.nb * c / nc), k1 = (int)((long long)sh.nb * (c + 1) / nc);
-                if (k1 <= k0) continue;
-                if (!d.ev_chunk[c]) HIP_TRY(ctx, hipEventCreateWithFlags(&d.ev_chunk[c], hipEventDisableTiming));
-                rc = trace_bands(ctx, d, d.stream, W, H, sh.band_rows, sh.first + k0 * sh.step, sh.step,
-                                 d.d_bands + (size_t)k0 * sh.band_rows * W, nullptr, RT_BANDS_INT32, 1, 0, nullptr,
-                                 nullptr, k1 - k0);
-                if (rc != RT_OK) return rc;
-                HIP_TRY(ctx, hipEventRecord(d.ev_chunk[c], d.stream));
-                HIP_TRY(ctx, hipStreamWaitEvent(d.copy_stream, d.ev_chunk[c], 0));
-                rc = runtime_band_copy(ctx, sh, W, H, d.d_bands, pixels, d.copy_stream, true, k0, k1);
-                if (rc != RT_OK) return rc;
-            }
+            RT_TRY(trace_and_copy_chunks(ctx, d, d.stream, sh, W, H, nc, d.d_bands, pixels, true));
             continue;
         }
         if (mode == TICK_RUNTIME || (nc == 1 && n == 1)) {  // the runtime's copy after the trace
-            rc = trace_bands(ctx, d, d.stream, W, H, sh.band_rows, sh.first, sh.step, d.d_bands, nullptr);
-            if (rc != RT_OK) return rc;
+            RT_TRY(trace_bands(ctx, d, d.stream, share_req(sh, W, H, 0, sh.nb, d.d_bands)));
             const bool ctimed = begin_timed(ctx, d, 1);
-            rc = runtime_band_copy(ctx, sh, W, H, d.d_bands, pixels, d.stream, mapped != nullptr);
+            const int rc = runtime_band_copy(ctx, sh, W, H, d.d_bands, pixels, d.stream, mapped != nullptr, 0, sh.nb);
             end_timed(d, ctimed);
             if (rc != RT_OK) return rc;
             continue;
         }
         CopyJob prev{};
         for (int c = 0; c < nc; ++c) {
-            const int k0 = (int)((long long)sh.nb * c / nc), k1 = (int)((long long)sh.nb * (c + 1) / nc);
-            if (k1 <= k0) continue;
-            int32_t* out = d.d_bands + (size_t)k0 * sh.band_rows * W;
-            rc = trace_bands(ctx, d, d.stream, W, H, sh.band_rows, sh.first + k0 * sh.step, sh.step, out, nullptr,
-                             RT_BANDS_INT32, 1, 0, nullptr, &prev, k1 - k0);
-            if (rc != RT_OK) return rc;
-            prev = share_job(sh, W, H, k0, k1, out, mapped);
+            const Bands b = chunk_bands(sh, c, nc);
+            if (b.k1 <= b.k0) continue;
+            const TraceReq q = share_req(sh, W, H, b.k0, b.k1, d.d_bands, &prev);
+            RT_TRY(trace_bands(ctx, d, d.stream, q));
+            prev = share_job(sh, W, H, b.k0, b.k1, q.out, mapped);
         }
         const bool ctimed = begin_timed(ctx, d, 1);
         const int e = launch_band_copy(prev, d.stream);
@@ -2300,33 +2356,24 @@ int tick_sync(rt_ctx* ctx, int W, int H, int32_t* pixels) {
 
 // Tick(): full frame into the caller's Surface.pixels, synchronous.
 int rt_render(rt_ctx* ctx, int width, int height, int32_t* pixels) {
-    int rc = check_ctx(ctx, width, height);
-    if (rc != RT_OK) return rc;
+    RT_TRY(check_ctx(ctx, width, height));
     if (!pixels) return fail(ctx, RT_ERR_INVALID_ARG, "NULL pixels");
-    for (const Device& d : ctx->dev)
-        if (d.hand.job.words || d.copy_pending[0] || d.copy_pending[1]) {  // rt_render_async frames first (the
-            rc = rt_wait(ctx);                                             // caller may reuse their buffers)
-            if (rc != RT_OK) return rc;
-            break;
-        }
+    RT_TRY(wait_pending_async(ctx));
     if (ctx->rccl_gather) {  // bands gathered to device 0 over RCCL, then the whole frame over its link
         Device& d0 = ctx->dev[0];
         const size_t frame_bytes = (size_t)width * height * sizeof(int32_t);
         {
             DeviceGuard guard(d0.id);
-            rc = grow(ctx, (void**)&d0.d_frame, &d0.frame_cap, frame_bytes);
-            if (rc != RT_OK) return rc;
+            RT_TRY(grow(ctx, (void**)&d0.d_frame, &d0.frame_cap, frame_bytes));
         }
-        rc = gather_frame(ctx, width, height, d0.d_frame);
-        if (rc != RT_OK) return rc;
+        RT_TRY(gather_frame(ctx, width, height, d0.d_frame));
         DeviceGuard guard(d0.id);
         const bool ctimed = begin_timed(ctx, d0, 1);
         HIP_TRY(ctx, hipMemcpyAsync(pixels, d0.d_frame, frame_bytes, hipMemcpyDeviceToHost, d0.stream));
         end_timed(d0, ctimed);
         HIP_TRY(ctx, hipStreamSynchronize(d0.stream));
     } else {
-        rc = tick_sync(ctx, width, height, pixels);
-        if (rc != RT_OK) return rc;
+        RT_TRY(tick_sync(ctx, width, height, pixels));
     }
     ctx->frames++;
     ctx->pixels += (uint64_t)width * (uint64_t)height;
@@ -2334,11 +2381,6 @@ int rt_render(rt_ctx* ctx, int width, int height, int32_t* pixels) {
 }
 
 namespace {
-// Bytes of one frame's output of a band render in `fmt`.
-size_t band_output_bytes(int W, int H, int nb, int band_rows, int fmt) {
-    return fmt == RT_BANDS_FRAME ? (size_t)W * H * 4 : (size_t)nb * band_rows * W * (fmt == RT_BANDS_RGB24 ? 3 : 4);
-}
-
 // The launch of a camera-path call: n_frames frames (grid z), frame f with the view of cams[f].  The views are
 // built on the host by view_fill -- the code behind every one-camera launch -- packed as DevView records into
 // a table slot's pinned staging buffer and uploaded on `stream` ahead of the launch.  The context's camera and
@@ -2355,7 +2397,7 @@ int trace_path(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const r
         HIP_TRY(ctx, hipEventSynchronize(ps.done));
         ps.busy = false;
     }
-    if (!ps.done) HIP_TRY(ctx, hipEventCreateWithFlags(&ps.done, hipEventDisableTiming));
+    RT_TRY(ensure_event(ctx, &ps.done));
     // (a slot keeps its buffers for the next call, but no more than PATH_SLOT_KEEP records of them: a call that
     // needs fewer finds a larger table shrunk to its own size, so one long path does not pin its tables for good)
     if (ps.cap < (size_t)n_frames || (ps.cap > Device::PATH_SLOT_KEEP && (size_t)n_frames <= Device::PATH_SLOT_KEEP)) {
@@ -2413,18 +2455,15 @@ int check_path(rt_ctx* ctx, const char* who, int W, int H, const rt_camera* cams
 int rt_render_path_bands(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames, int band_rows,
                          int band_first, int band_step, void* d_out, size_t frame_stride_bytes, int format,
                          void* hip_stream, int* out_n_bands) {
-    int rc = check_path(ctx, "rt_render_path_bands", width, height, cameras, n_frames);
-    if (rc != RT_OK) return rc;
-    if (band_rows <= 0 || band_first < 0 || band_step <= 0 || !d_out ||
-        (format != RT_BANDS_INT32 && format != RT_BANDS_RGB24 && format != RT_BANDS_FRAME))
-        return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_path_bands: bad band arguments");
+    RT_TRY(check_path(ctx, "rt_render_path_bands", width, height, cameras, n_frames));
+    RT_TRY(check_band_args(ctx, "rt_render_path_bands", band_rows, band_first, band_step, d_out, format));
     const int nb = bands_of(height, band_rows, band_first, band_step);
     if (n_frames > 1 && frame_stride_bytes < band_output_bytes(width, height, nb, band_rows, format))
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_path_bands: frame stride smaller than a frame's output");
     Device& d = ctx->dev[0];
     DeviceGuard guard(d.id);
-    rc = trace_path(ctx, d, (hipStream_t)hip_stream, width, height, cameras, n_frames, band_rows, band_first, band_step,
-                    d_out, frame_stride_bytes, format);
+    const int rc = trace_path(ctx, d, (hipStream_t)hip_stream, width, height, cameras, n_frames, band_rows, band_first,
+                              band_step, d_out, frame_stride_bytes, format);
     if (out_n_bands) *out_n_bands = nb;
     if (rc == RT_OK) ctx->pixels += (uint64_t)nb * band_rows * width * (uint64_t)n_frames;
     return rc;
@@ -2437,22 +2476,19 @@ int rt_render_path(rt_ctx* ctx, int width, int height, const rt_camera* cameras,
     int rc = check_path(ctx, "rt_render_path", width, height, cameras, n_frames);
     if (rc != RT_OK) return rc;
     if (!pixels) return fail(ctx, RT_ERR_INVALID_ARG, "NULL pixels");
+    RT_TRY(wait_pending_async(ctx));
     Device& d = ctx->dev[0];
-    if (d.hand.job.words || d.copy_pending[0] || d.copy_pending[1]) {  // rt_render_async frames first
-        rc = rt_wait(ctx);
-        if (rc != RT_OK) return rc;
-    }
     DeviceGuard guard(d.id);
     const size_t frame_bytes = (size_t)width * height * sizeof(int32_t);
     const size_t fit = std::max<size_t>(1, ((size_t)256 << 20) / frame_bytes);
     const int chunk = (int)std::min<size_t>((size_t)n_frames, ctx->path_chunk_frames > 0 ? (size_t)ctx->path_chunk_frames : fit);
     const int n_chunks = (n_frames + chunk - 1) / chunk;
-    if (!d.copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking));
+    RT_TRY(ensure_stream(ctx, &d.copy_stream));
+    hipEvent_t* const traced = &d.ev[Device::EV_PATH_TRACED], * const copied = &d.ev[Device::EV_PATH_COPIED];
     for (int i = 0; i < std::min(2, n_chunks); ++i) {
-        rc = grow(ctx, (void**)&d.d_path[i], &d.path_cap[i], (size_t)chunk * frame_bytes);
-        if (rc != RT_OK) return rc;
-        if (!d.ev_path_traced[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&d.ev_path_traced[i], hipEventDisableTiming));
-        if (!d.ev_path_copied[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&d.ev_path_copied[i], hipEventDisableTiming));
+        RT_TRY(grow(ctx, (void**)&d.d_path[i], &d.path_cap[i], (size_t)chunk * frame_bytes));
+        RT_TRY(ensure_event(ctx, &traced[i]));
+        RT_TRY(ensure_event(ctx, &copied[i]));
     }
     // Every failure inside the loop leaves through the two synchronisations below: copies already queued into
     // `pixels` have landed (or failed) before this synchronous call returns, whatever it returns.
@@ -2462,17 +2498,17 @@ int rt_render_path(rt_ctx* ctx, int width, int height, const rt_camera* cameras,
     };
     for (int c = 0; c < n_chunks; ++c) {
         const int f0 = c * chunk, nf = std::min(chunk, n_frames - f0), b = c & 1;
-        if (c >= 2 && !hip_ok(hipStreamWaitEvent(d.stream, d.ev_path_copied[b], 0), "hipStreamWaitEvent")) break;
+        if (c >= 2 && !hip_ok(hipStreamWaitEvent(d.stream, copied[b], 0), "hipStreamWaitEvent")) break;
         rc = trace_path(ctx, d, d.stream, width, height, cameras + f0, nf, height, 0, 1, d.d_path[b], frame_bytes,
                         RT_BANDS_INT32);
         if (rc != RT_OK) break;
         // (into a range that is not registered the runtime stages this copy and the call returns only when it is
         // done: chunk c + 1 is then traced after the copy of chunk c, not under it)
-        if (!hip_ok(hipEventRecord(d.ev_path_traced[b], d.stream), "hipEventRecord") ||
-            !hip_ok(hipStreamWaitEvent(d.copy_stream, d.ev_path_traced[b], 0), "hipStreamWaitEvent") ||
+        if (!hip_ok(hipEventRecord(traced[b], d.stream), "hipEventRecord") ||
+            !hip_ok(hipStreamWaitEvent(d.copy_stream, traced[b], 0), "hipStreamWaitEvent") ||
             !hip_ok(hipMemcpyAsync(pixels + (size_t)f0 * width * height, d.d_path[b], (size_t)nf * frame_bytes,
                                    hipMemcpyDeviceToHost, d.copy_stream), "hipMemcpyAsync") ||
-            !hip_ok(hipEventRecord(d.ev_path_copied[b], d.copy_stream), "hipEventRecord"))
+            !hip_ok(hipEventRecord(copied[b], d.copy_stream), "hipEventRecord"))
             break;
     }
     const hipError_t e_trace = hipStreamSynchronize(d.stream), e_copy = hipStreamSynchronize(d.copy_stream);
@@ -2495,8 +2531,7 @@ int rt_render_path(rt_ctx* ctx, int width, int height, const rt_camera* cameras,
 // stream / D2H-on-another pattern does the same -- while one stream ran a steady 195-200 us with
 // the runtime's copy and 184-187 us with the copy slice.
 int rt_render_async(rt_ctx* ctx, int width, int height, int32_t* pixels) {
-    int rc = check_ctx(ctx, width, height);
-    if (rc != RT_OK) return rc;
+    RT_TRY(check_ctx(ctx, width, height));
     if (!pixels) return fail(ctx, RT_ERR_INVALID_ARG, "NULL pixels");
     if (ctx->rccl_gather) return rt_render(ctx, width, height, pixels);
     const size_t frame_bytes = (size_t)width * height * sizeof(int32_t);
@@ -2513,69 +2548,50 @@ int rt_render_async(rt_ctx* ctx, int width, int height, int32_t* pixels) {
     for (int g = 0; g < n; ++g) {
         Device& d = ctx->dev[(size_t)g];
         DeviceGuard guard(d.id);
-        if (!d.async_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.async_stream, hipStreamNonBlocking));
+        RT_TRY(ensure_stream(ctx, &d.async_stream));
         const int slot = d.async_next;
         const Share sh = share_of(width, height, g, n, nc > 1);
         const size_t bytes = std::max<size_t>(1, (size_t)sh.nb * sh.band_rows * width) * sizeof(int32_t);
-        if (d.frames2_cap[slot] < bytes || sh.nb <= 0) {  // (re)allocation: the pending copy may read the
-            rc = flush_hand(ctx);                         // other buffer only, but nothing may still use
-            if (rc != RT_OK) return rc;                   // this one
+        // (re)allocation: the pending copy may read the other buffer only, but nothing may still use this one
+        if (d.frames2_cap[slot] < bytes || sh.nb <= 0) {
+            RT_TRY(flush_hand(ctx));
             HIP_TRY(ctx, hipStreamSynchronize(d.async_stream));
             if (d.copy_stream) HIP_TRY(ctx, hipStreamSynchronize(d.copy_stream));
             d.copy_pending[0] = d.copy_pending[1] = false;
         }
         if (sh.nb <= 0) continue;  // (more workers than bands)
-        rc = grow(ctx, (void**)&d.d_frames2[slot], &d.frames2_cap[slot], bytes);
-        if (rc != RT_OK) return rc;
+        RT_TRY(grow(ctx, (void**)&d.d_frames2[slot], &d.frames2_cap[slot], bytes));
         if (engine) {
-            if (!d.copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking));
-            for (int i = 0; i < 2; ++i) {
-                if (!d.ev_traced[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&d.ev_traced[i], hipEventDisableTiming));
-                if (!d.ev_copied[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&d.ev_copied[i], hipEventDisableTiming));
-            }
-            rc = flush_hand(ctx);  // (a slice-mode frame still pending)
-            if (rc != RT_OK) return rc;
+            hipEvent_t& copied = d.ev[Device::EV_COPIED + slot];
+            hipEvent_t* const ring = &d.ev[Device::EV_RING];
+            RT_TRY(ensure_event(ctx, &copied));
+            RT_TRY(flush_hand(ctx));  // (a slice-mode frame still pending)
             const uint64_t f = d.frames_issued++;
             const int cap = ctx->tick_inflight;
-            if (cap > 0 && f >= (uint64_t)cap && d.ev_ring[(f - cap) % Device::RING])  // at most cap frames queued
-                HIP_TRY(ctx, hipEventSynchronize(d.ev_ring[(f - cap) % Device::RING]));
-            if (d.copy_pending[slot]) HIP_TRY(ctx, hipStreamWaitEvent(d.async_stream, d.ev_copied[slot], 0));
+            if (cap > 0 && f >= (uint64_t)cap && ring[(f - cap) % Device::RING])  // at most cap frames queued
+                HIP_TRY(ctx, hipEventSynchronize(ring[(f - cap) % Device::RING]));
+            if (d.copy_pending[slot]) HIP_TRY(ctx, hipStreamWaitEvent(d.async_stream, copied, 0));
             const bool pinned = mapped_host(ctx, g, pixels, frame_bytes) != nullptr;
-            for (int c = 0; c < nc; ++c) {
-                const int k0 = (int)((long long)sh.nb * c / nc), k1 = (int)((long long)sh.nb * (c + 1) / nc);
-                if (k1 <= k0) continue;
-                hipEvent_t& ev = nc > 1 ? d.ev_chunk[c] : d.ev_traced[slot];
-                if (!ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                rc = trace_bands(ctx, d, d.async_stream, width, height, sh.band_rows, sh.first + k0 * sh.step, sh.step,
-                                 d.d_frames2[slot] + (size_t)k0 * sh.band_rows * width, nullptr, RT_BANDS_INT32, 1, 0,
-                                 nullptr, nullptr, k1 - k0);
-                if (rc != RT_OK) return rc;
-                HIP_TRY(ctx, hipEventRecord(ev, d.async_stream));
-                HIP_TRY(ctx, hipStreamWaitEvent(d.copy_stream, ev, 0));
-                rc = runtime_band_copy(ctx, sh, width, height, d.d_frames2[slot], pixels, d.copy_stream, pinned, k0, k1);
-                if (rc != RT_OK) return rc;
-            }
-            HIP_TRY(ctx, hipEventRecord(d.ev_copied[slot], d.copy_stream));
+            RT_TRY(trace_and_copy_chunks(ctx, d, d.async_stream, sh, width, height, nc, d.d_frames2[slot], pixels, pinned));
+            HIP_TRY(ctx, hipEventRecord(copied, d.copy_stream));
             if (cap > 0) {
-                hipEvent_t& er = d.ev_ring[f % Device::RING];
-                if (!er) HIP_TRY(ctx, hipEventCreateWithFlags(&er, hipEventDisableTiming));
+                hipEvent_t& er = ring[f % Device::RING];
+                RT_TRY(ensure_event(ctx, &er));
                 HIP_TRY(ctx, hipEventRecord(er, d.copy_stream));
             }
             d.copy_pending[slot] = true;
             d.async_next = slot ^ 1;
             continue;
         }
-        rc = trace_bands(ctx, d, d.async_stream, width, height, sh.band_rows, sh.first, sh.step, d.d_frames2[slot],
-                         nullptr, RT_BANDS_INT32, 1, 0, nullptr, d.hand.job.words ? &d.hand.job : nullptr);
-        if (rc != RT_OK) return rc;
+        // (the pending hand-off as the launch's copy slice; none while it holds no words)
+        RT_TRY(trace_bands(ctx, d, d.async_stream, share_req(sh, width, height, 0, sh.nb, d.d_frames2[slot], &d.hand.job)));
         d.hand = {};  // issued (in the launch)
         int32_t* mapped = mapped_host(ctx, g, pixels, frame_bytes);
         if (mapped) {
             d.hand.host = sh.step == 1 ? pixels : nullptr;
             d.hand.job = share_job(sh, width, height, 0, sh.nb, d.d_frames2[slot], mapped);
         } else {
-            rc = runtime_band_copy(ctx, sh, width, height, d.d_frames2[slot], pixels, d.async_stream);
-            if (rc != RT_OK) return rc;
+            RT_TRY(runtime_band_copy(ctx, sh, width, height, d.d_frames2[slot], pixels, d.async_stream, false, 0, sh.nb));
         }
         d.async_next = slot ^ 1;
     }
