@@ -55,7 +55,7 @@ struct Tally {
     }
 };
 
-// The kernels' exact fast paths of Math.Pow (rt_kernel.hip spec_pow: n = 1 -> x, n = 2 -> x * x in binary32,
+// The kernels' exact fast paths of Math.Pow (rt_prims.h spec_pow: n = 1 -> x, n = 2 -> x * x in binary32,
 // n = 0.5 -> binary32 sqrt) against glibc's (float)pow for EVERY binary32 x in [0, 1 + 16 ulp].
 static int fast_paths(unsigned nt) {
     std::vector<long> bad(nt, 0);

@@ -17,7 +17,9 @@
 // correctly rounded division is correct iff b*mid_lo < a < b*mid_hi for the midpoints
 // around it, evaluated exactly in binary64).  Outside the domains (denormals, huge
 // values, zeros, inf, NaN) the guarded wrappers fall back to the generic operation, so
-// every input gives the generic result bit for bit.
+// every input gives the generic result bit for bit.  The checker is the full sweep, run by hand; on every GPU
+// run tests/test_gpu_prims.py pins sqrt_cr, rcp_cr, inv_len_cr and div_cr (and the generic operations) against
+// float64 rounded once, at every exponent, the subnormals, the special values and each domain bound's neighbours.
 #pragma once
 #include <hip/hip_runtime.h>
 

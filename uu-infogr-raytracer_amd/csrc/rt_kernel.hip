@@ -28,6 +28,7 @@
 #include "rt_dark.h"
 #include "rt_internal.h"
 #include "rt_pow.h"
+#include "rt_prims.h"
 #include "rt_resolve.h"
 
 // One wave (64 lanes, an 8x8 pixel tile) per workgroup: a one-wave group releases its LDS
@@ -38,183 +39,6 @@
 constexpr int WG_THREADS = 64, TILE_W = 8, TILE_H = 8;
 
 namespace rtk {
-
-// Correctly rounded binary32 operations.  Vector3.Normalize's 1f / MathF.Sqrt(x) runs the short
-// sequence of rt_fastmath.h inside its verified domain (the same bits as the generic sequence for
-// every input, tools/fastmath_check.hip); the same treatment of the other sqrt and of division
-// measured slower (profiles/ab/r01_fastmath.txt), so they use the generic operations.
-__device__ __forceinline__ float cr_sqrt(float x) { return __builtin_sqrtf(x); }
-__device__ __forceinline__ float cr_inv_len(float x) { return inv_len_cr(x); }  // 1f / MathF.Sqrt(x)
-__device__ __forceinline__ float cr_rcp(float x) { return 1.0f / x; }
-
-struct f3 {
-    float x, y, z;
-};
-
-__device__ __forceinline__ f3 mk(float x, float y, float z) { return f3{x, y, z}; }
-__device__ __forceinline__ f3 add(f3 a, f3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ f3 sub(f3 a, f3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ f3 mul(f3 a, f3 b) { return mk(a.x * b.x, a.y * b.y, a.z * b.z); }
-__device__ __forceinline__ f3 scale(f3 a, float s) { return mk(a.x * s, a.y * s, a.z * s); }
-// Vector3.Dot: (x*x') + (y*y') + (z*z')
-__device__ __forceinline__ float dot(f3 a, f3 b) { return ((a.x * b.x) + (a.y * b.y)) + (a.z * b.z); }
-// Vector3.Normalize: s = 1f / MathF.Sqrt(x*x + y*y + z*z); v * s
-__device__ __forceinline__ f3 normalize(f3 a) {
-    const float s = cr_inv_len(dot(a, a));
-    return scale(a, s);
-}
-// Math.Max(x, 0f) / Math.Min(a, b) on .NET Core 3.0+: IEEE 754-2019 maximum / minimum
-// (NaN propagates, -0 < +0) -> v_maximum3_f32 / v_minimum3_f32 on gfx950.
-__device__ __forceinline__ float nmax0(float a) { return __builtin_elementwise_maximum(a, 0.0f); }
-__device__ __forceinline__ float nmin(float a, float b) { return __builtin_elementwise_minimum(a, b); }
-
-// (int)float on .NET 6 x64 (cvttss2si): NaN or out of range -> int.MinValue.
-__device__ __forceinline__ int32_t net_f2i(float v) {
-    return (v >= -2147483648.0f && v < 2147483648.0f) ? (int32_t)v : (int32_t)0x80000000;
-}
-
-// glibc's pow tables (rt_pow.h, generated by tools/gen_pow_tables.py), in global memory: read per lane
-// (the table index depends on the lane's x), only by the GPOW instantiations.
-__device__ const glibc_pow_data::LogEntry g_pow_log[128] = RT_POW_LOG_TAB;
-__device__ const uint64_t g_pow_exp[256] = RT_POW_EXP_TAB;
-
-// (float)Math.Pow((double)x, (double)n) for the shading exponent (RayTracer.cs:691; Math.Pow = glibc's pow on
-// Linux x64).  Exact fast paths: n == 1 -> x; n == 2 -> x*x (the double product of two floats is exact, so one
-// float rounding of it equals binary32 x*x); n == 0.5 -> binary32 sqrt (a double result within glibc pow's
-// 0.52 ulp can never straddle a binary32 rounding boundary of sqrt(float): the exact root is >= 2^-49 relative
-// away from every binary32 midpoint) -- all three equal glibc's (float)pow for every binary32 x in [0, 1 + 16
-// ulp] (tests/native/pow_host.cpp fast-paths).  Other exponents run glibc's own algorithm (rt_pow.h, bit for bit
-// the host's pow; the device's ocml pow rounds differently near float midpoints, profiles/r06_pow_check.txt),
-// compiled in only when the scene needs it.
-template <bool GPOW>
-__device__ __forceinline__ float spec_pow(float x, uint32_t kind, float n) {
-    switch (kind) {
-        case POW_ONE: return x;
-        case POW_HALF: return cr_sqrt(x);
-        case POW_TWO: return x * x;
-        default:
-            if constexpr (GPOW) return (float)glibc_pow((double)x, (double)n, g_pow_log, g_pow_exp);
-            else return x;  // unreachable: the host selects GPOW when any material needs it
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// IntersectsSphere (RayTracer.cs:613-642) for nearest-hit selection, epsilon 0.
-//
-// The reference returns dist = min(max(t1,0), max(t2,0)) on a collision (dist > 0) and 0
-// otherwise, with t2 = (-b+sqrt)/2a, t1 = (-b-sqrt)/2a; the callers then select only
-// dist > 0 (TracePixel :977) or dist - 0.01 > 0 (TraceSecondaryRay :804).  When 2a is
-// finite and > 0 (always, for the normalised primary and reflected directions) the
-// exactly-rounded results satisfy t2 >= t1 (numerators ordered, rounding and division by
-// a positive number monotonic), so a selectable distance exists iff t1 > 0, and then it is
-// t1 itself.  t1 > 0 iff fl(-b - sq) > 0 iff -b > sq (gradual underflow), which needs
-// -b > 0 first.  So: no sqrt when b >= 0, never the t2 division.  Returns the reference's
-// distance when it is selectable and otherwise a value <= 0 or NaN, which every caller's
-// selection test (t > 0, t - 0.01 > 0) rejects exactly as it rejects the reference's 0:
-// fl(-b - sq) <= 0 whenever -b <= sq (and NaN when disc < 0), and dividing by the positive
-// 2a keeps the sign -- identical selections and identical winning distances.
-//
-// Scalar-issue economy (MI355X: one scalar unit per CU serves its 4 SIMDs, ~1 SALU
-// instruction per CU-cycle against ~1.8 VALU, profiles/r02_issue_probe.txt): the sqrt and the
-// division run under a wave-uniform branch on the ballot of the candidate lanes instead of an
-// exec-mask if/else, and the result needs no select.
-// ---------------------------------------------------------------------------------
-__device__ __forceinline__ bool sphere_candidate(float b, float disc) {
-    // disc >= 0 && b <= 0 (b = +-0 cannot select: -b > sq fails); NaN -> false
-    return __builtin_elementwise_minimum(disc, -b) >= 0.0f;
-}
-__device__ __forceinline__ float root_t1(float b, float disc, float a2) {
-    float t = 0.0f;
-    if (__builtin_amdgcn_ballot_w64(sphere_candidate(b, disc)) != 0) {  // wave-uniform
-        const float sq = cr_sqrt(disc);  // == (float)Math.Sqrt((double)disc); NaN off-candidate
-        t = (-b - sq) / a2;              // t1 = (-b - sqrt) / 2a, :630
-    }
-    return t;
-}
-
-// Literal formula, for directions whose 2a is not finite-positive.
-__device__ __forceinline__ float root_full(float b, float disc, float a2) {
-    float t = 0.0f;
-    if (disc >= 0.0f) {
-        const float sq = __builtin_sqrtf(disc);
-        const float t2 = (-b + sq) / a2;
-        const float t1 = (-b - sq) / a2;
-        t = nmin(nmax0(t1), nmax0(t2));
-    }
-    return t;
-}
-
-// A2OK: 2a is finite and > 0 for every active lane (checked once per segment with a ballot,
-// so the sphere loops carry no per-lane two-way split).
-template <bool A2OK>
-__device__ __forceinline__ float root_sel(float b, float disc, float a2, bool a2_ok) {
-    if constexpr (A2OK) return root_t1(b, disc, a2);
-    else return a2_ok ? root_t1(b, disc, a2) : root_full(b, disc, a2);
-}
-template <bool A2OK>
-__device__ __forceinline__ float sphere_t(f3 o, f3 d, float a2, float a4, bool a2_ok, const DevSphere& s) {
-    const f3 oc = sub(o, mk(s.cx, s.cy, s.cz));
-    const float b = 2.0f * dot(oc, d);
-    const float c = dot(oc, oc) - s.r2;
-    const float disc = b * b - a4 * c;
-    return root_sel<A2OK>(b, disc, a2, a2_ok);
-}
-
-// Shadow ray of IntersectShadowLight (origin = hit point, direction = light POSITION,
-// epsilon 0.001, RayTracer.cs:574-578): collision iff min(max(t1-e,0), max(t2-e,0)) > 0.
-// With 2a finite-positive (uniform per light) and t2 >= t1 that is t1 - e > 0 (and then
-// t2 - e > 0 too); fl(-b - sq) / 2a - e > 0 already implies -b > sq (see root_t1).
-// THRESH: the same predicate without the division -- t1 - e > 0 iff fl(-b - sq) >= l.sh_t, the
-// per-light threshold of the correctly rounded quotient (rt_api.cpp shadow_threshold; NaN
-// compares false, as the reference's NaN distance does).  Used by the bundle kernel (C4 -3 % with
-// paired candidates); in the direct kernel the division-free form measured slower (C2 +4 %, C3
-// +6 %: the shading code around it was scheduled worse), so it keeps the division there.
-template <bool A2OK, bool THRESH = false>
-__device__ __forceinline__ bool shadow_decide(float b, float disc, const DevLight& l, bool a2_ok) {
-    if (A2OK || a2_ok) {
-        bool hit = false;
-        if (__builtin_amdgcn_ballot_w64(sphere_candidate(b, disc)) != 0) {  // wave-uniform
-            const float sq = cr_sqrt(disc);
-            if constexpr (THRESH) hit = -b - sq >= l.sh_t;  // == fl(fl(-b - sq) / 2a) - 0.001f > 0
-            else hit = (-b - sq) / l.a2 - 0.001f > 0.0f;
-        }
-        return hit;
-    }
-    if (disc >= 0.0f) {
-        const float sq = __builtin_sqrtf(disc);
-        const float t2 = (-b + sq) / l.a2;
-        const float t1 = (-b - sq) / l.a2;
-        return nmin(nmax0(t1 - 0.001f), nmax0(t2 - 0.001f)) > 0.0f;
-    }
-    return false;
-}
-template <bool A2OK, bool THRESH = false>
-__device__ __forceinline__ bool shadow_blocked(f3 hp, const DevLight& l, bool a2_ok, const DevSphere& s) {
-    const f3 oc = sub(hp, mk(s.cx, s.cy, s.cz));
-    const float b = 2.0f * dot(oc, mk(l.px, l.py, l.pz));
-    const float c = dot(oc, oc) - s.r2;
-    const float disc = b * b - l.a4 * c;
-    return shadow_decide<A2OK, THRESH>(b, disc, l, a2_ok);
-}
-
-
-// IntersectPlane, RayTracer.cs:590-604: t = (((-o.x*n.x) - o.y*n.y) - o.z*n.z + c.n) / d.n,
-// hit iff t > 0 -- the quotient itself.  (+inf, from a zero denominator, is a "hit" that no
-// nearest-plane search can select: the best distance starts at +inf and the test is strict.)
-__device__ __forceinline__ float plane_t(f3 o, f3 d, const DevPlane& p) {
-    const float num = ((-o.x * p.nx - o.y * p.ny) - o.z * p.nz) + p.cn;
-    const float den = dot(d, mk(p.nx, p.ny, p.nz));
-    return num / den;
-}
-
-// ShiftColor, :1046-1052: Math.Clamp (NaN passes), * 255f, Math.Floor, (int), (byte).
-// Branch-free: IEEE maxNum/minNum return the non-NaN operand, so NaN -> 0 -> byte 0, the
-// byte .NET gives ((int)NaN = int.MinValue, (byte) of it = 0); +-inf clamp to 1 / 0 and -0
-// gives 0 as in the reference.
-__device__ __forceinline__ uint32_t shift_channel(float c) {
-    const float cl = __builtin_fminf(__builtin_fmaxf(c, 0.0f), 1.0f);
-    return (uint32_t)(int32_t)__builtin_floorf(cl * 255.0f);
-}
 
 // Frame / band output: int32 0x00RRGGBB at the packed band row r (format 0) or at the frame
 // row y (format 2), or packed 24-bit (B, G, R bytes; the top byte of the int32 is always 0)
@@ -792,7 +616,7 @@ __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere
         // checkerboard, :766-770: ((int)u + (int)v) & 1, unchecked int add
         const float u = dot(mk(pl.e1x, pl.e1y, pl.e1z), hp);
         const float v = dot(mk(pl.e2x, pl.e2y, pl.e2z), hp);
-        tile = (float)(int32_t)(((uint32_t)net_f2i(u) + (uint32_t)net_f2i(v)) & 1u);
+        tile = checker_tile(u, v);
         dark = (flags & MAT_DARK_OK) != 0 && dark_lane_ok(hp.x, hp.y, hp.z, t, dot(d, d), tile);
     }
     f3 col = mk(0.0f, 0.0f, 0.0f);
@@ -800,7 +624,7 @@ __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere
     if ((flags & MAT_DIFFUSE) && !dark) {
         const f3 view = normalize(d);  // ShapePhongShading :668 (not negated)
         // sphere: (1 / t) * t (:866);  plane: (float)(1 / Math.Pow(t, 2)) (:754), exact as 1/(t*t) in f64
-        const float att = is_sphere ? cr_rcp(t) * t : (float)(1.0 / ((double)t * (double)t));
+        const float att = is_sphere ? sphere_att(t) : plane_att(t);
         const f3 kd = mk(m.kd[0], m.kd[1], m.kd[2]);
         // the material's specular terms once, not per light under the MAT_SPEC branch
         const f3 ks = mk(m.ks[0], m.ks[1], m.ks[2]);
@@ -1684,7 +1508,7 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
         const DevPlane& pl = p.pl[prim];
         const float u = dot(mk(pl.e1x, pl.e1y, pl.e1z), hp);
         const float v = dot(mk(pl.e2x, pl.e2y, pl.e2z), hp);
-        tile = (float)(int32_t)(((uint32_t)net_f2i(u) + (uint32_t)net_f2i(v)) & 1u);
+        tile = checker_tile(u, v);
         dark = (flags & MAT_DARK_OK) != 0 && dark_lane_ok(hp.x, hp.y, hp.z, t, dot(d, d), tile);
     }
     const bool lit = diff && !dark;
@@ -1731,7 +1555,7 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
     if (__builtin_amdgcn_ballot_w64(lit) != 0) {
         const f3 view = normalize(d);  // ShapePhongShading :668 (not negated)
         // sphere: (1 / t) * t (:866);  plane: (float)(1 / Math.Pow(t, 2)) (:754), exact as 1/(t*t) in f64
-        const float att = is_sphere ? cr_rcp(t) * t : (float)(1.0 / ((double)t * (double)t));
+        const float att = is_sphere ? sphere_att(t) : plane_att(t);
         const f3 kd = mk(m.kd[0], m.kd[1], m.kd[2]);
         const f3 ks = mk(m.ks[0], m.ks[1], m.ks[2]);  // once, not per light under the MAT_SPEC branch
         const uint32_t pk = m.pow_kind;
