@@ -306,6 +306,28 @@ int rt_render_path_bands(rt_ctx* ctx, int width, int height, const rt_camera* ca
                          size_t frame_stride_bytes, int format, void* hip_stream, int* out_n_bands);
 int rt_render_path(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames,
                    int32_t* pixels);
+/* (ABI 10 addition) Camera-path shutter: every output frame is the mean of `shutter` sub-frame cameras, taken
+ * inside the trace kernel -- motion blur, or temporal anti-aliasing by jittered cameras, at no extra output.
+ * `cameras` has n_frames * shutter entries; sub-frame (f, s) is the frame rt_render_bands_ex would write with
+ * cameras[f * shutter + s] set, and output frame f is, per 8-bit channel and after ShiftColor, the round-half-up
+ * mean of its sub-frames: (sum + shutter / 2) >> log2(shutter).  A wave traces its tile once per sub-frame and
+ * keeps the running sums in registers: no sub-frame reaches memory, and the output keeps a path render's size.
+ *   - shutter is a power of two in 1..RT_MAX_SHUTTER, and n_frames * shutter <= RT_MAX_PATH_FRAMES; otherwise
+ *     RT_ERR_INVALID_ARG.  shutter == 1 is rt_render_path_bands / rt_render_path itself (the same launches).
+ *   - Everything else is as for the path calls: formats, frame_stride_bytes, rt_set_view_height, the context's
+ *     camera left alone, natural tile order, single-GPU contexts only, RT_ERR_UNSUPPORTED while supersampling.
+ *   - Statistics: frames and pixels count output frames and pixels, launches one per launch; with counting on,
+ *     primary_rays grows by the traced pixels x n_frames x shutter and reflect_rays / shadow_rays by the sum
+ *     over every sub-frame (each sub-frame counts for itself); with counting off nothing grows.
+ * rt_render_shutter: whole output frames into host memory, pixels[n_frames][height][width], synchronous, through
+ * rt_render_path's chunk pipeline: RT_PATH_CHUNK_FRAMES and the 256 MiB rule count output frames, and a
+ * chunk's view table holds chunk * shutter records. */
+#define RT_MAX_SHUTTER 256   /* 256 * 255 + 128 = 65,408 < 65,536: a channel's sum fits a 16-bit field */
+int rt_render_shutter_bands(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames,
+                            int shutter, int band_rows, int band_first, int band_step, void* d_out,
+                            size_t frame_stride_bytes, int format, void* hip_stream, int* out_n_bands);
+int rt_render_shutter(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames,
+                      int shutter, int32_t* pixels);
 /* Reassemble the band sets of `world` ranks (band b rendered by rank b % world with
  * band_first = rank, band_step = world), gathered rank after rank at slot_bytes intervals
  * in d_gathered, into the row-major frame d_frame[height][width] -- one launch for all

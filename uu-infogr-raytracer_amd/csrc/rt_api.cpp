@@ -2381,15 +2381,31 @@ int rt_render(rt_ctx* ctx, int width, int height, int32_t* pixels) {
 }
 
 namespace {
+// The view table of a path launch: record i = the view of cams[i], in the cameras' own order (with a shutter of m,
+// sub-frame s of output frame f is camera and record f * m + s).  lp: the launch's block, which comes out with the
+// view of the last camera and the fields every camera shares (pw, ph, nearc, W).  No device call.
+int view_table_fill(rt_ctx* ctx, const rt_camera* cams, int n_views, int W, int VH, LaunchParams& lp, DevView* table) {
+    for (int i = 0; i < n_views; ++i) {
+        const int rc = view_fill(ctx, cams[i], W, VH, lp);
+        if (rc != RT_OK) return rc;
+        view_record(lp, table[i]);
+    }
+    return RT_OK;
+}
+
 // The launch of a camera-path call: n_frames frames (grid z), frame f with the view of cams[f].  The views are
 // built on the host by view_fill -- the code behind every one-camera launch -- packed as DevView records into
 // a table slot's pinned staging buffer and uploaded on `stream` ahead of the launch.  The context's camera and
 // its view cache (view_lp) are not touched.  Natural tile order, one tile per workgroup, whatever n_frames.
 // Nothing here waits for the device except a slot's own event; the shared view tables (view_tables) are rebuilt,
 // with that function's synchronisation, only when the frame size changes, and a slot's buffers are reallocated
-// only when a call brings more frames than the slot holds, or finds it holding more than PATH_SLOT_KEEP.
-int trace_path(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const rt_camera* cams, int n_frames,
+// only when a call brings more records than the slot holds, or finds it holding more than PATH_SLOT_KEEP.
+// With a shutter (rt_render_shutter_bands, t = log2 of it > 0) the table holds n_frames << t records, sub-frame s
+// of output frame f at f << t | s = cams' own order, and the launch -- still n_frames frames in grid z -- averages
+// each frame's 1 << t records in the kernel (LaunchParams::shutter_log2); t = 0 is the path launch itself.
+int trace_path(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const rt_camera* cams, int n_frames, int t,
                int band_rows, int first, int step, void* out, size_t frame_bytes, int fmt) {
+    const int n_views = n_frames << t;  // (the callers bound it by RT_MAX_PATH_FRAMES)
     const int VH = ctx->view_height > 0 ? ctx->view_height : H;
     if (H > VH) return fail(ctx, RT_ERR_INVALID_ARG, "frame height %d above the view height %d", H, ctx->view_height);
     Device::PathSlot& ps = d.path_slot[d.path_next++ % Device::PATH_SLOTS];
@@ -2400,40 +2416,38 @@ int trace_path(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const r
     RT_TRY(ensure_event(ctx, &ps.done));
     // (a slot keeps its buffers for the next call, but no more than PATH_SLOT_KEEP records of them: a call that
     // needs fewer finds a larger table shrunk to its own size, so one long path does not pin its tables for good)
-    if (ps.cap < (size_t)n_frames || (ps.cap > Device::PATH_SLOT_KEEP && (size_t)n_frames <= Device::PATH_SLOT_KEEP)) {
+    if (ps.cap < (size_t)n_views || (ps.cap > Device::PATH_SLOT_KEEP && (size_t)n_views <= Device::PATH_SLOT_KEEP)) {
         if (ps.h_views) (void)hipHostFree(ps.h_views);
         if (ps.d_views) (void)hipFree(ps.d_views);
         ps.h_views = nullptr, ps.d_views = nullptr, ps.cap = 0;
-        const size_t bytes = (size_t)n_frames * sizeof(DevView);
+        const size_t bytes = (size_t)n_views * sizeof(DevView);
         hipError_t e = hipHostMalloc((void**)&ps.h_views, bytes, hipHostMallocDefault);
         if (e == hipSuccess) e = hipMalloc((void**)&ps.d_views, bytes);
         if (e != hipSuccess) {
             if (ps.h_views) (void)hipHostFree(ps.h_views);
             ps.h_views = nullptr;
-            return fail(ctx, RT_ERR_OOM, "view table of %d frames: %s", n_frames, hipGetErrorString(e));
+            return fail(ctx, RT_ERR_OOM, "view table of %d frames: %s", n_views, hipGetErrorString(e));
         }
-        ps.cap = (size_t)n_frames;
+        ps.cap = (size_t)n_views;
     }
     LaunchParams lp;
     std::memset(&lp, 0, sizeof lp);
-    for (int f = 0; f < n_frames; ++f) {
-        const int rc = view_fill(ctx, cams[f], W, VH, lp);
-        if (rc != RT_OK) return rc;
-        view_record(lp, ps.h_views[f]);
-    }
+    int rc = view_table_fill(ctx, cams, n_views, W, VH, lp, ps.h_views);
+    if (rc != RT_OK) return rc;
     lp.H = H;  // the rows traced; pw, ph, nearc and W are the same for every camera (lxt / lyt: view_tables)
     scene_params(ctx, d, lp);
-    int rc = view_tables(ctx, d, lp);
+    rc = view_tables(ctx, d, lp);
     if (rc != RT_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ps.d_views, ps.h_views, (size_t)n_frames * sizeof(DevView), hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ps.d_views, ps.h_views, (size_t)n_views * sizeof(DevView), hipMemcpyHostToDevice, stream));
     const int nb = bands_of(H, band_rows, first, step);
     lp.views = ps.d_views;
+    lp.shutter_log2 = t;
     lp.band_first = first, lp.band_step = step, lp.band_rows = band_rows, lp.local_rows = nb * band_rows;
     lp.out = (int32_t*)out;
     lp.out_fmt = fmt;
     lp.n_frames = n_frames;
     lp.out_frame_bytes = frame_bytes;
-    rc = launch_counted(ctx, d, stream, lp, "path", W, H, band_rows, first, step, nb, n_frames, 0);
+    rc = launch_counted(ctx, d, stream, lp, "path", W, H, band_rows, first, step, nb, n_views, 0);  // (primary rays: every sub-frame's)
     if (rc != RT_OK) return rc;
     HIP_TRY(ctx, hipEventRecord(ps.done, stream));
     ps.busy = true;
@@ -2450,30 +2464,66 @@ int check_path(rt_ctx* ctx, const char* who, int W, int H, const rt_camera* cams
     if (ctx->ss_log2 > 0) return fail(ctx, RT_ERR_UNSUPPORTED, "%s does not supersample", who);
     return RT_OK;
 }
-}  // namespace
 
-int rt_render_path_bands(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames, int band_rows,
-                         int band_first, int band_step, void* d_out, size_t frame_stride_bytes, int format,
-                         void* hip_stream, int* out_n_bands) {
-    RT_TRY(check_path(ctx, "rt_render_path_bands", width, height, cameras, n_frames));
-    RT_TRY(check_band_args(ctx, "rt_render_path_bands", band_rows, band_first, band_step, d_out, format));
+// The shutter calls' own arguments, ahead of check_path's: *t = log2(shutter).  n_frames * shutter cameras make
+// one view table, so their product keeps the bound of a path's frames.
+int check_shutter(rt_ctx* ctx, const char* who, int n_frames, int shutter, int* t) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "NULL context");
+    if (shutter < 1 || shutter > RT_MAX_SHUTTER || (shutter & (shutter - 1)) != 0)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: shutter %d is not a power of two in 1..%d", who, shutter, RT_MAX_SHUTTER);
+    if (n_frames > 0 && (long long)n_frames * shutter > RT_MAX_PATH_FRAMES)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: %d frames x shutter %d above %d cameras", who, n_frames, shutter,
+                    RT_MAX_PATH_FRAMES);
+    *t = 0;
+    while ((1 << *t) < shutter) ++*t;
+    return RT_OK;
+}
+
+// rt_render_path_bands and rt_render_shutter_bands (t = log2 of the shutter) after their argument checks.
+int path_bands(rt_ctx* ctx, const char* who, int width, int height, const rt_camera* cameras, int n_frames, int t,
+               int band_rows, int band_first, int band_step, void* d_out, size_t frame_stride_bytes, int format,
+               void* hip_stream, int* out_n_bands) {
+    RT_TRY(check_path(ctx, who, width, height, cameras, n_frames));
+    RT_TRY(check_band_args(ctx, who, band_rows, band_first, band_step, d_out, format));
     const int nb = bands_of(height, band_rows, band_first, band_step);
     if (n_frames > 1 && frame_stride_bytes < band_output_bytes(width, height, nb, band_rows, format))
-        return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_path_bands: frame stride smaller than a frame's output");
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: frame stride smaller than a frame's output", who);
     Device& d = ctx->dev[0];
     DeviceGuard guard(d.id);
-    const int rc = trace_path(ctx, d, (hipStream_t)hip_stream, width, height, cameras, n_frames, band_rows, band_first,
+    const int rc = trace_path(ctx, d, (hipStream_t)hip_stream, width, height, cameras, n_frames, t, band_rows, band_first,
                               band_step, d_out, frame_stride_bytes, format);
     if (out_n_bands) *out_n_bands = nb;
     if (rc == RT_OK) ctx->pixels += (uint64_t)nb * band_rows * width * (uint64_t)n_frames;
     return rc;
 }
+}  // namespace
+
+int rt_render_path_bands(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames, int band_rows,
+                         int band_first, int band_step, void* d_out, size_t frame_stride_bytes, int format,
+                         void* hip_stream, int* out_n_bands) {
+    return path_bands(ctx, "rt_render_path_bands", width, height, cameras, n_frames, 0, band_rows, band_first, band_step,
+                      d_out, frame_stride_bytes, format, hip_stream, out_n_bands);
+}
+
+// shutter == 1 (t = 0) is the path call: the same launch, the PATH kernels.
+int rt_render_shutter_bands(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames, int shutter,
+                            int band_rows, int band_first, int band_step, void* d_out, size_t frame_stride_bytes,
+                            int format, void* hip_stream, int* out_n_bands) {
+    int t = 0;
+    RT_TRY(check_shutter(ctx, "rt_render_shutter_bands", n_frames, shutter, &t));
+    return path_bands(ctx, t ? "rt_render_shutter_bands" : "rt_render_path_bands", width, height, cameras, n_frames, t,
+                      band_rows, band_first, band_step, d_out, frame_stride_bytes, format, hip_stream, out_n_bands);
+}
 
 // Chunks of at most path_chunk_frames frames: chunk c is traced into d_path[c % 2] on the worker's stream and
 // copied out by the copy engine on copy_stream once its trace event has fired, under the trace of chunk c + 1;
 // the trace of chunk c + 2 waits for that copy (the Tick pattern of tick_sync's chunks, over frames).
-int rt_render_path(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames, int32_t* pixels) {
-    int rc = check_path(ctx, "rt_render_path", width, height, cameras, n_frames);
+// rt_render_path and rt_render_shutter (t = log2 of the shutter: frames, chunks and buffers are output frames, and
+// a chunk's launch takes its chunk << t cameras).
+namespace {
+int path_frames(rt_ctx* ctx, const char* who, int width, int height, const rt_camera* cameras, int n_frames, int t,
+                int32_t* pixels) {
+    int rc = check_path(ctx, who, width, height, cameras, n_frames);
     if (rc != RT_OK) return rc;
     if (!pixels) return fail(ctx, RT_ERR_INVALID_ARG, "NULL pixels");
     RT_TRY(wait_pending_async(ctx));
@@ -2493,14 +2543,14 @@ int rt_render_path(rt_ctx* ctx, int width, int height, const rt_camera* cameras,
     // Every failure inside the loop leaves through the two synchronisations below: copies already queued into
     // `pixels` have landed (or failed) before this synchronous call returns, whatever it returns.
     auto hip_ok = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess) rc = fail(ctx, RT_ERR_HIP, "rt_render_path: %s failed: %s", what, hipGetErrorString(e));
+        if (e != hipSuccess) rc = fail(ctx, RT_ERR_HIP, "%s: %s failed: %s", who, what, hipGetErrorString(e));
         return e == hipSuccess;
     };
     for (int c = 0; c < n_chunks; ++c) {
         const int f0 = c * chunk, nf = std::min(chunk, n_frames - f0), b = c & 1;
         if (c >= 2 && !hip_ok(hipStreamWaitEvent(d.stream, copied[b], 0), "hipStreamWaitEvent")) break;
-        rc = trace_path(ctx, d, d.stream, width, height, cameras + f0, nf, height, 0, 1, d.d_path[b], frame_bytes,
-                        RT_BANDS_INT32);
+        rc = trace_path(ctx, d, d.stream, width, height, cameras + ((size_t)f0 << t), nf, t, height, 0, 1, d.d_path[b],
+                        frame_bytes, RT_BANDS_INT32);
         if (rc != RT_OK) break;
         // (into a range that is not registered the runtime stages this copy and the call returns only when it is
         // done: chunk c + 1 is then traced after the copy of chunk c, not under it)
@@ -2517,6 +2567,18 @@ int rt_render_path(rt_ctx* ctx, int width, int height, const rt_camera* cameras,
     ctx->frames += (uint64_t)n_frames;
     ctx->pixels += (uint64_t)width * (uint64_t)height * (uint64_t)n_frames;
     return RT_OK;
+}
+}  // namespace
+
+int rt_render_path(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames, int32_t* pixels) {
+    return path_frames(ctx, "rt_render_path", width, height, cameras, n_frames, 0, pixels);
+}
+
+int rt_render_shutter(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames, int shutter,
+                      int32_t* pixels) {
+    int t = 0;
+    RT_TRY(check_shutter(ctx, "rt_render_shutter", n_frames, shutter, &t));
+    return path_frames(ctx, t ? "rt_render_shutter" : "rt_render_path", width, height, cameras, n_frames, t, pixels);
 }
 
 // Double-buffered Tick() on one in-order stream per worker.  Frame k's band set is traced into device

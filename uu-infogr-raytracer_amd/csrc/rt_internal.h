@@ -252,8 +252,13 @@ struct LaunchParams {
     PrimBox mbox[2][CULL_MIN_SPHERES];
     // Camera-path launches (rt_render_path_bands): frame z of the grid takes its view from views[z] instead of
     // cam .. fwd, prim_const, pc, pbox and mbox* above (the PATH instantiations, rt_kernel.hip); nullptr: every
-    // frame has the view above.  Last: no other field moves.
+    // frame has the view above.  After every earlier field: none of them moves.
     const DevView* views;
+    // The shutter of a camera-path launch (rt_render_shutter_bands, the SHUTTER instantiations): log2 of the
+    // cameras m averaged per output frame, 0 = an ordinary path launch.  With it set `views` holds n_frames << t
+    // records, sub-frame s of grid z at views[z << t | s], and a wave traces its tile once per sub-frame and stores
+    // the round-half-up mean (rt_resolve.h resolve_round_n).  Last: no other field moves.
+    int shutter_log2;
 };
 constexpr int MIRROR_BOX_PLANES = 2;
 // Tiles per workgroup of the direct kernel's single-frame launches (8: +2.5 % on C2,
@@ -276,8 +281,9 @@ constexpr int DIRECT_SMAX = 8;
 
 enum : int { TV_DIRECT = 0, TV_BUNDLE = 1 };
 // PLAIN: pixels to `out`.  STATS: as PLAIN, and the diagnostic tallies of the executed work.  TILES: out_fmt
-// OUT_TILES, the fused tile encoder.  SS: the supersampling epilogue.  PATH: one DevView per grid z.
-enum : int { TM_PLAIN = 0, TM_STATS = 1, TM_TILES = 2, TM_SS = 3, TM_PATH = 4 };
+// OUT_TILES, the fused tile encoder.  SS: the supersampling epilogue.  PATH: one DevView per grid z.  SHUTTER: a
+// PATH launch whose waves average 1 << shutter_log2 DevViews per grid z.
+enum : int { TM_PLAIN = 0, TM_STATS = 1, TM_TILES = 2, TM_SS = 3, TM_PATH = 4, TM_SHUTTER = 5 };
 struct TraceVariant {
     int family;  // TV_*
     int gpow;    // some material needs the f64 Math.Pow path: the entry points without the register caps
@@ -288,7 +294,7 @@ struct TraceVariant {
     int tord;    // 0: tiles in grid order (row_order / col_major), 1: tile_order, 2: as 0 and tile_cost recorded
 };
 
-enum : unsigned { VF_GPOW = 1u, VF_STATS = 2u, VF_TILES = 4u, VF_SS = 8u, VF_PATH = 16u };
+enum : unsigned { VF_GPOW = 1u, VF_STATS = 2u, VF_TILES = 4u, VF_SS = 8u, VF_PATH = 16u, VF_SHUTTER = 32u };
 constexpr unsigned vf_cls(int c) { return (unsigned)c << 8; }
 constexpr unsigned vf_wpg(int w) { return (unsigned)w << 12; }
 constexpr unsigned vf_tord(int t) { return (unsigned)t << 16; }
@@ -298,8 +304,8 @@ constexpr int vf_tord_of(unsigned v) { return (int)(v >> 16 & 3u); }
 static_assert(DIRECT_SMAX < 16 && SINGLE_WPG < 16, "the variant word's 4-bit fields");
 constexpr unsigned variant_word(const TraceVariant& v) {
     return (v.gpow ? VF_GPOW : 0u) | (v.mode == TM_STATS ? VF_STATS : 0u) | (v.mode == TM_TILES ? VF_TILES : 0u) |
-           (v.mode == TM_SS ? VF_SS : 0u) | (v.mode == TM_PATH ? VF_PATH : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) |
-           vf_tord(v.tord);
+           (v.mode == TM_SS ? VF_SS : 0u) | (v.mode == TM_PATH ? VF_PATH : 0u) |
+           (v.mode == TM_SHUTTER ? VF_SHUTTER : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
 }
 
 // The bundle family's shadow pass by scene: 0 = per light (also every scene of the direct family), 1 = the
@@ -310,9 +316,10 @@ inline int merged_class(int S, int L, bool lights_a2_ok) {
     return lights_a2_ok ? 2 : 1;
 }
 
-// The instantiations that exist (384): every mode, depth and class of both families at one tile per workgroup
-// in grid order; the direct kernel's lone-frame workgroups of SINGLE_WPG tiles in each tile order (PLAIN
-// only); the all-lights-ok merged bundle kernel's tile orders (PLAIN, no GPOW).
+// The instantiations that exist (444): every mode, depth and class of both families at one tile per workgroup
+// in grid order (SHUTTER among them, under PATH's conditions: 60 of its own); the direct kernel's lone-frame
+// workgroups of SINGLE_WPG tiles in each tile order (PLAIN only); the all-lights-ok merged bundle kernel's tile
+// orders (PLAIN, no GPOW).
 constexpr bool trace_variant_built(const TraceVariant& v) {
     const bool plain = v.mode == TM_PLAIN;
     if (v.family == TV_DIRECT)
@@ -324,10 +331,11 @@ constexpr bool trace_variant_built(const TraceVariant& v) {
 // hipErrorInvalidValue; rt_api.cpp refuses these before any launch).  No device call.
 inline bool pick_trace_variant(const LaunchParams& p, bool generic_pow, bool stats, TraceVariant* v) {
     const bool tiles = p.out_fmt == OUT_TILES, ordered = p.tile_order != nullptr || p.tile_cost != nullptr;
+    if (p.shutter_log2 != 0 && (p.views == nullptr || p.shutter_log2 < 0 || p.shutter_log2 > 8)) return false;
     if (p.views != nullptr) {
         if (p.ss_log2 > 0 || tiles || stats || ordered || p.copy_z != 0 || p.row_order_n != 0 || p.col_major != 0)
             return false;
-        v->mode = TM_PATH;
+        v->mode = p.shutter_log2 > 0 ? TM_SHUTTER : TM_PATH;
     } else if (p.ss_log2 > 0) {
         if (p.ss_log2 > 3 || tiles || stats || ordered) return false;
         v->mode = TM_SS;

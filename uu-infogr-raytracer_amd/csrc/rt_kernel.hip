@@ -198,52 +198,60 @@ __device__ __forceinline__ void encode_tile_fused(const LaunchParams& p, uint32_
 // -- is read from the frame's DevView record in device memory instead of the kernarg block.  blockIdx.z is
 // wave-uniform, so the reads stay scalar loads (the kernarg block itself is read with scalar loads too: the
 // same instructions from another base address).  The values are those a one-camera launch would carry.
-template <bool PATH>
+// SHUTTER (rt_render_shutter_bands): grid z is an output frame that averages 1 << shutter_log2 sub-frames, and the
+// wave traces them one after the other; the sub-frame's record index `rec` = z << shutter_log2 | s travels with the
+// ViewOf as a member, from the kernel body's loop counter through every function that builds one.  It is made of
+// blockIdx.z, a kernarg and a wave-uniform loop counter only, so it lives in an SGPR and the reads stay scalar
+// loads.  The other views never read `rec` (it is a dead constant 0 there: their code is what it was).
+constexpr int VIEW_ARGS = 0, VIEW_PATH = 1, VIEW_SHUTTER = 2;
+constexpr int view_of(unsigned V) { return (V & VF_SHUTTER) ? VIEW_SHUTTER : (V & VF_PATH) ? VIEW_PATH : VIEW_ARGS; }
+template <int PATH>
 struct ViewOf {
     const LaunchParams& p;
-    __device__ __forceinline__ const DevView& v() const { return p.views[blockIdx.z]; }
+    int rec = 0;
+    __device__ __forceinline__ const DevView& v() const { return p.views[PATH == VIEW_SHUTTER ? (unsigned)rec : blockIdx.z]; }
     __device__ __forceinline__ f3 cam() const {
-        if constexpr (PATH) return mk(v().cam[0], v().cam[1], v().cam[2]);
+        if constexpr (PATH != VIEW_ARGS) return mk(v().cam[0], v().cam[1], v().cam[2]);
         else return mk(p.cam[0], p.cam[1], p.cam[2]);
     }
     __device__ __forceinline__ f3 right() const {
-        if constexpr (PATH) return mk(v().right[0], v().right[1], v().right[2]);
+        if constexpr (PATH != VIEW_ARGS) return mk(v().right[0], v().right[1], v().right[2]);
         else return mk(p.right[0], p.right[1], p.right[2]);
     }
     __device__ __forceinline__ f3 up() const {
-        if constexpr (PATH) return mk(v().up[0], v().up[1], v().up[2]);
+        if constexpr (PATH != VIEW_ARGS) return mk(v().up[0], v().up[1], v().up[2]);
         else return mk(p.up[0], p.up[1], p.up[2]);
     }
     __device__ __forceinline__ f3 fwd() const {
-        if constexpr (PATH) return mk(v().fwd[0], v().fwd[1], v().fwd[2]);
+        if constexpr (PATH != VIEW_ARGS) return mk(v().fwd[0], v().fwd[1], v().fwd[2]);
         else return mk(p.fwd[0], p.fwd[1], p.fwd[2]);
     }
     __device__ __forceinline__ int prim_const() const {
-        if constexpr (PATH) return v().prim_const;
+        if constexpr (PATH != VIEW_ARGS) return v().prim_const;
         else return p.prim_const;
     }
     __device__ __forceinline__ const PrimConst* pc() const {
-        if constexpr (PATH) return v().pc;
+        if constexpr (PATH != VIEW_ARGS) return v().pc;
         else return p.pc;
     }
     __device__ __forceinline__ const PrimBox* pbox() const {
-        if constexpr (PATH) return v().pbox;
+        if constexpr (PATH != VIEW_ARGS) return v().pbox;
         else return p.pbox;
     }
     __device__ __forceinline__ int mbox_n() const {
-        if constexpr (PATH) return v().mbox_n;
+        if constexpr (PATH != VIEW_ARGS) return v().mbox_n;
         else return p.mbox_n;
     }
     __device__ __forceinline__ int mbox_plane(int k) const {
-        if constexpr (PATH) return v().mbox_plane[k];
+        if constexpr (PATH != VIEW_ARGS) return v().mbox_plane[k];
         else return p.mbox_plane[k];
     }
     __device__ __forceinline__ float mbox_tmax(int k) const {
-        if constexpr (PATH) return v().mbox_tmax[k];
+        if constexpr (PATH != VIEW_ARGS) return v().mbox_tmax[k];
         else return p.mbox_tmax[k];
     }
     __device__ __forceinline__ const PrimBox* mbox(int k) const {
-        if constexpr (PATH) return v().mbox[k];
+        if constexpr (PATH != VIEW_ARGS) return v().mbox[k];
         else return p.mbox[k];
     }
 };
@@ -261,8 +269,8 @@ struct ScratchStack {
         b[n] = y;
         ++n;
     }
-    template <bool PATH = false>
-    __device__ __forceinline__ void pop(const LaunchParams&, float4& x, float4& y) {
+    template <int PATH = VIEW_ARGS>
+    __device__ __forceinline__ void pop(const LaunchParams&, float4& x, float4& y, int = 0) {
         --n;
         x = a[n];
         y = b[n];
@@ -307,10 +315,10 @@ struct LdsStack {
         lv[n * WG_THREADS + (threadIdx.x & 63)] = make_float2(x.w, y.w);
         ++n;
     }
-    template <bool PATH = false>
-    __device__ __forceinline__ void pop(const LaunchParams& p, float4& x, float4& y) {
+    template <int PATH = VIEW_ARGS>
+    __device__ __forceinline__ void pop(const LaunchParams& p, float4& x, float4& y, int rec = 0) {
         --n;
-        f3 o = ViewOf<PATH>{p}.cam();
+        f3 o = ViewOf<PATH>{p, rec}.cam();
         f3 d = mk(dv[(threadIdx.x & 63)], dv[WG_THREADS + (threadIdx.x & 63)], dv[2 * WG_THREADS + (threadIdx.x & 63)]);
 #pragma unroll 1
         for (int j = 0; j < K - 1; ++j) {
@@ -433,8 +441,9 @@ struct Tally<true, SMAX> {
 // over 8192 slots instead of 256 changed nothing, profiles/r05_bundle_lone.txt) -- so a
 // display loop that never reads rt_get_stats turns them off (rt_set_counting, ABI 10).
 // PATH (camera-path launches): every frame has its own camera and so its own counts -- each z counts for
-// itself, an atomic pair per wave per frame (counting off spares them as in any launch).
-template <bool ST, bool PATH = false, int SM>
+// itself, an atomic pair per wave per frame (counting off spares them as in any launch).  SHUTTER: shutter_tile
+// counts, every sub-frame for itself, and adds the wave's totals once.
+template <bool ST, int PATH = VIEW_ARGS, int SM>
 __device__ __forceinline__ void add_counters(const LaunchParams& p, int lane, unsigned n_refl, unsigned n_shadow,
                                              const Tally<ST, SM>& tl) {
     // wave-uniform: the first frame (behind a copy slice) counts, and only when the context counts at all
@@ -677,17 +686,17 @@ __device__ __forceinline__ unsigned long long box_mask(const LaunchParams& p, co
     const bool cand = in & (b.x0 <= x_hi) & (b.x1 >= x_lo) & (b.y0 <= y_hi) & (b.y1 >= y_lo);
     return __builtin_amdgcn_ballot_w64(cand);
 }
-template <bool PATH = false>
-__device__ __forceinline__ unsigned long long prim_box_mask(const LaunchParams& p, int x, int y) {
-    return box_mask(p, ViewOf<PATH>{p}.pbox(), x, y);
+template <int PATH = VIEW_ARGS>
+__device__ __forceinline__ unsigned long long prim_box_mask(const LaunchParams& p, int x, int y, int rec = 0) {
+    return box_mask(p, ViewOf<PATH>{p, rec}.pbox(), x, y);
 }
 // Candidate spheres of the wave's first reflected segments off the boxed mirror planes (LaunchParams::mbox,
 // rt_api.cpp mirror_boxes): table k's mask in bits [16 k, 16 k + S) of one wave-uniform word (S < CULL_MIN_SPHERES
 // <= 16).  A lane whose primary hit is plane mbox_plane[k] with t <= mbox_tmax[k] reflects into a ray that can
 // select only those spheres.  Converged call; 0 without tables.
-template <bool PATH = false>
-__device__ __forceinline__ unsigned mirror_box_masks(const LaunchParams& p, int x, int y) {
-    const ViewOf<PATH> vw{p};
+template <int PATH = VIEW_ARGS>
+__device__ __forceinline__ unsigned mirror_box_masks(const LaunchParams& p, int x, int y, int rec = 0) {
+    const ViewOf<PATH> vw{p, rec};
     unsigned m = 0;
     if (vw.mbox_n() > 0) {  // wave-uniform
         m = (unsigned)box_mask(p, vw.mbox(0), x, y);
@@ -698,9 +707,9 @@ __device__ __forceinline__ unsigned mirror_box_masks(const LaunchParams& p, int 
 // The sphere mask of a wave's first reflected segment, chosen by the lanes still walking (divergent call, every
 // active lane at count 1; t, prim: the lane's primary hit): every sphere when some lane left a sphere, a plane
 // without a table or a plane beyond its t_max (NaN included), else the OR of the tables of the planes that were hit.
-template <bool PATH = false>
-__device__ __forceinline__ unsigned mirror_box_select(const LaunchParams& p, unsigned masks, float t, int prim) {
-    const ViewOf<PATH> vw{p};
+template <int PATH = VIEW_ARGS>
+__device__ __forceinline__ unsigned mirror_box_select(const LaunchParams& p, unsigned masks, float t, int prim, int rec = 0) {
+    const ViewOf<PATH> vw{p, rec};
     const int pi = ~prim;  // plane index; a sphere's (prim >= 0) is excluded below: ~0 would match an unused table's -1
     const bool on0 = prim < 0 && pi == vw.mbox_plane(0) && t <= vw.mbox_tmax(0);
     const bool on1 = prim < 0 && pi == vw.mbox_plane(1) && t <= vw.mbox_tmax(1);
@@ -750,17 +759,17 @@ __device__ __forceinline__ TilePixel tile_pixel(const LaunchParams& p, int x, in
 // (mirror_box_select; all ones: every sphere) and a pair runs only when one of its bits is set -- a skipped
 // sphere's test yields t <= 0 or NaN on every active lane, which take_secondary rejects, and the kept ones are
 // still visited in ascending index.
-template <bool PRIMARY, bool A2OK, bool GATED = false, bool PATH = false, typename T>
+template <bool PRIMARY, bool A2OK, bool GATED = false, int PATH = VIEW_ARGS, typename T>
 __device__ __forceinline__ void nearest_spheres(const LaunchParams& p, f3 o, f3 d, float a2, float a4, bool a2_ok,
-                                                unsigned long long pmask, float& best_s, int& win_s, T& tl) {
-    if (PRIMARY && ViewOf<PATH>{p}.prim_const()) {
+                                                unsigned long long pmask, float& best_s, int& win_s, T& tl, int rec = 0) {
+    if (PRIMARY && ViewOf<PATH>{p, rec}.prim_const()) {
         // o == camera: oc = cam - c and c = oc.oc - r^2 are the same per frame (:614-619);
         // only the wave's candidate spheres, in ascending order (non-candidates give t <= 0)
         for (unsigned long long m = pmask; m;) {
             const int i = (int)__builtin_ctzll(m);
             m &= ~(1ull << i);
             tl.sphere(true);
-            const PrimConst pc = ViewOf<PATH>{p}.pc()[i];
+            const PrimConst pc = ViewOf<PATH>{p, rec}.pc()[i];
             const float b = 2.0f * dot(mk(pc.ocx, pc.ocy, pc.ocz), d);
             const float disc = b * b - a4 * pc.c;
             const float t = A2OK ? root_t1(b, disc, a2) : (a2_ok ? root_t1(b, disc, a2) : root_full(b, disc, a2));
@@ -788,17 +797,18 @@ __device__ __forceinline__ void nearest_spheres(const LaunchParams& p, f3 o, f3 
     }
 }
 
-template <bool PRIMARY, bool GATED = false, bool PATH = false, typename T>
-__device__ __forceinline__ Hit nearest_direct(const LaunchParams& p, f3 o, f3 d, T& tl, unsigned long long pmask = 0) {
+template <bool PRIMARY, bool GATED = false, int PATH = VIEW_ARGS, typename T>
+__device__ __forceinline__ Hit nearest_direct(const LaunchParams& p, f3 o, f3 d, T& tl, unsigned long long pmask = 0,
+                                              int rec = 0) {
     const float a = dot(d, d);
     const float a2 = 2.0f * a, a4 = 4.0f * a;
     const bool a2_ok = a2 > 0.0f && a2 < __builtin_inff();
     float best_s = __builtin_inff();
     int win_s = -1;
     if (__builtin_amdgcn_ballot_w64(!a2_ok) == 0)  // wave-uniform (the usual case)
-        nearest_spheres<PRIMARY, true, GATED, PATH>(p, o, d, a2, a4, a2_ok, pmask, best_s, win_s, tl);
+        nearest_spheres<PRIMARY, true, GATED, PATH>(p, o, d, a2, a4, a2_ok, pmask, best_s, win_s, tl, rec);
     else
-        nearest_spheres<PRIMARY, false, GATED, PATH>(p, o, d, a2, a4, a2_ok, pmask, best_s, win_s, tl);
+        nearest_spheres<PRIMARY, false, GATED, PATH>(p, o, d, a2, a4, a2_ok, pmask, best_s, win_s, tl, rec);
     float best_p = __builtin_inff();
     int win_p = -1;
     for (int i = 0; i < p.P; ++i) {
@@ -843,21 +853,30 @@ __device__ __forceinline__ Hit terminal_direct(const LaunchParams& p, f3 o, f3 d
 // masked by it, so one instantiation serves every shape and order.
 constexpr unsigned VF_TILE = ~(vf_wpg(15) | vf_tord(3));
 
+// What the trace of one tile hands back: the lane's packed counts, reflected segments (bits 0-7) | shadow rays
+// << 8, and its pixel 0x00RRGGBB (outside the frame: a value nobody stores).  SHUTTER: the tile trace neither stores nor encodes -- the
+// pixel goes back to the kernel body's sub-frame loop (shutter_tile), which stores the mean.
+struct TileOut {
+    unsigned cnt;
+    uint32_t px32;
+};
+
 // DIRECT path, one 8x8 tile: each lane walks its own chain with per-lane (divergent) control
-// flow.  Returns the lane's packed counts: reflected segments (bits 0-7) | shadow rays << 8.
+// flow.  rec: the sub-frame's view record (SHUTTER only, wave-uniform; see ViewOf).
 template <int K, unsigned V, typename T>
-__device__ __forceinline__ unsigned trace_tile_direct(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
-                                                      float* stk_dv, T& tl) {
-    constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = (V & VF_SS) != 0, PATH = (V & VF_PATH) != 0;
+__device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
+                                                     float* stk_dv, T& tl, int rec = 0) {
+    constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = (V & VF_SS) != 0, SHUTTER = (V & VF_SHUTTER) != 0;
+    constexpr int PATH = view_of(V);
     const int lane = threadIdx.x & 63;
     const TilePixel tpx = tile_pixel<SS>(p, tile_x * TILE_W + (lane & 7), tile_y * TILE_H + (lane >> 3));
     const int x = tpx.x, r = tpx.r, y = tpx.y;
     const bool valid = tpx.valid;
-    const ViewOf<PATH> vw{p};
-    const unsigned long long pmask = vw.prim_const() ? prim_box_mask<PATH>(p, x, y) : 0;
+    const ViewOf<PATH> vw{p, rec};
+    const unsigned long long pmask = vw.prim_const() ? prim_box_mask<PATH>(p, x, y, rec) : 0;
     // K == 1 (limit 0): level 1 is a terminal segment, nothing of the mirrored boxes is compiled in
     unsigned mmask = 0;
-    if constexpr (K > 1) mmask = mirror_box_masks<PATH>(p, x, y);
+    if constexpr (K > 1) mmask = mirror_box_masks<PATH>(p, x, y, rec);
 
     unsigned cnt = 0;  // packed: reflected segments (bits 0-7) | shadow rays << CNT_SHADOW_SHIFT
     typename StackFor<K>::type stk(stk_lv, stk_dv);
@@ -874,7 +893,7 @@ __device__ __forceinline__ unsigned trace_tile_direct(const LaunchParams& p, int
         f3 o = cam;
 
         stk.origin(d);
-        Hit h = nearest_direct<true, false, PATH>(p, o, d, tl, pmask);
+        Hit h = nearest_direct<true, false, PATH>(p, o, d, tl, pmask, rec);
         int count = 0;
         for (;;) {
             if (h.prim == HIT_NONE) break;      // nothing hit: plane colour stays Zero
@@ -898,7 +917,7 @@ __device__ __forceinline__ unsigned trace_tile_direct(const LaunchParams& p, int
                 // the first reflected segment: the spheres its mirrored boxes allow (when the wave has tables)
                 // (count read from the first active lane: a scalar branch, and the mask stays wave-uniform)
                 unsigned smask = ~0u;
-                if (vw.mbox_n() > 0 && __builtin_amdgcn_readfirstlane(count) == 1) smask = mirror_box_select<PATH>(p, mmask, h.t, h.prim);
+                if (vw.mbox_n() > 0 && __builtin_amdgcn_readfirstlane(count) == 1) smask = mirror_box_select<PATH>(p, mmask, h.t, h.prim, rec);
                 h = count > p.limit ? terminal_direct(p, o, d, tl) : nearest_direct<false, true>(p, o, d, tl, smask);
             } else {
                 h = count > p.limit ? terminal_direct(p, o, d, tl) : nearest_direct<false>(p, o, d, tl);
@@ -912,18 +931,69 @@ __device__ __forceinline__ unsigned trace_tile_direct(const LaunchParams& p, int
         f3 col = leaf;
         while (stk.n > 0) {
             float4 ra, rb;
-            stk.template pop<PATH>(p, ra, rb);
+            stk.template pop<PATH>(p, ra, rb, rec);
             const int code = __float_as_int(rb.w);
             const bool is_s = code >= 0;
             col = shade_direct<GPOW>(p, is_s, is_s ? code : ~code, mk(ra.x, ra.y, ra.z),
                                            mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl);
         }
         px32 = (shift_channel(col.x) << 16) | (shift_channel(col.y) << 8) | shift_channel(col.z);
-        if constexpr (!TILES && !SS) store_pixel(p, r, y, x, px32);
+        if constexpr (!TILES && !SS && !SHUTTER) store_pixel(p, r, y, x, px32);
     }
     if constexpr (TILES) encode_tile_fused(p, px32, valid);
     if constexpr (SS) resolve_tile(p, r, y, x, valid, px32);
-    return cnt;
+    return TileOut{cnt, px32};
+}
+
+// SHUTTER (rt_render_shutter_bands): the wave's tile of output frame z = blockIdx.z is the mean of m = 1 <<
+// shutter_log2 sub-frames, traced one after the other by `trace(p, rec, tile_x, tile_y)` with the view record rec =
+// z << t | s.  The running per-channel sums (rt_resolve.h: two words of 16-bit fields, exact up to 256 sub-frames)
+// are the only vector values carried across the loop; the LDS / scratch level stack is the same for every
+// sub-frame.  A loop, not an unroll: the kernel holds one copy of the trace.  After it the lane's pixel position is
+// derived again from the lane id (as the bundle kernel does: nothing of it is kept live through the traces) and
+// valid lanes store the round-half-up mean in the launch's format.
+// Ray counts: each sub-frame's packed per-lane count (8 bits of reflected segments) is reduced over the wave on
+// its own (wave_count: scalar results) and the wave's totals are carried in scalar registers, 64 bits each; lane 0
+// adds them to the wave's counter slot once, after the loop.  Nothing is written to global memory inside the loop
+// -- no store, no atomic: the scene, view and table reads of the next sub-frame then remain loads that nothing in
+// the kernel has clobbered, which is what keeps them scalar loads (an atomic per sub-frame turned 83 of the direct
+// kernel's 101 scalar loads into per-lane vector loads, and so did a volatile asm, which counts as a write).
+// Hoisting: everything a trace derives from the launch parameters and the tile position alone is the same in every
+// sub-frame, and the compiler would compute it once ahead of the loop and keep it in registers across every trace
+// (measured: 75-81 VGPRs against PATH's 56-59 in the direct kernels, 6 waves per SIMD instead of 8, and VGPR spills
+// to scratch under the bundle kernels' 64-VGPR cap).  So each sub-frame gets both through an empty asm tied to the
+// loop counter -- the tile position, and the address of the launch parameters, which is the kernarg segment's own
+// (every trace kernel has the one argument) -- and reads and derives what it needs inside the sub-frame, as the one
+// trace of a PATH kernel does.  The asm emits no instruction.
+template <typename F>
+__device__ __forceinline__ void shutter_tile(const LaunchParams& p, int tile_x, int tile_y, F trace) {
+    const int t = p.shutter_log2, m = 1 << t;
+    const int rec0 = (int)(blockIdx.z << t);
+    const bool counting = p.counters != nullptr;  // wave-uniform
+    ResolveSum acc{0u, 0u};
+    unsigned long long n_refl = 0, n_shadow = 0;  // the wave's totals (wave-uniform)
+#pragma unroll 1
+    for (int s = 0; s < m; ++s) {  // wave-uniform
+        int tx = tile_x, ty = tile_y;
+        asm("" : "+s"(tx), "+s"(ty) : "s"(s));
+        const __attribute__((address_space(4))) LaunchParams* kp =
+            (const __attribute__((address_space(4))) LaunchParams*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm("" : "+s"(kp) : "s"(s));
+        const TileOut o = trace(*(const LaunchParams*)kp, rec0 | s, tx, ty);
+        acc = resolve_add(acc, resolve_unpack(o.px32));
+        if (counting) {
+            n_refl += wave_count(o.cnt & CNT_REFL_MASK);
+            n_shadow += wave_count(o.cnt >> CNT_SHADOW_SHIFT);
+        }
+    }
+    const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const TilePixel q = tile_pixel(p, tile_x * TILE_W + (ln & 7), tile_y * TILE_H + (ln >> 3));
+    if (q.valid) store_pixel(p, q.r, q.y, q.x, resolve_round_n(acc, t));
+    if (counting && ln == 0) {
+        unsigned long long* c = &p.counters[((blockIdx.y * gridDim.x + blockIdx.x) % COUNTER_SLOTS) * COUNTER_STRIDE];
+        if (n_refl) atomicAdd(c + CNT_REFLECT, n_refl);
+        if (n_shadow) atomicAdd(c + CNT_SHADOW, n_shadow);
+    }
 }
 
 // DIRECT kernel (scenes with < CULL_MIN_SPHERES spheres).
@@ -939,12 +1009,14 @@ __device__ __forceinline__ unsigned trace_tile_direct(const LaunchParams& p, int
 // their own: the order read and the recording, compiled into the common kernel even when unused, cost a
 // one-frame launch 2 % and 10 % (C2 19.9 -> 20.3 / 22.4 us, profiles/ab/r05_tile_order.txt).
 // SS: the supersampling epilogue (resolve_tile) in place of the pixel stores.  PATH: frame z of the grid takes its
-// view from LaunchParams::views (one DevView per grid z).  Both of the plain batch variants only (no STATS, no
-// TILES, WPG 1, TORD 0: rt_internal.h trace_variant_built).
+// view from LaunchParams::views (one DevView per grid z).  SHUTTER: a PATH launch whose waves trace 1 <<
+// shutter_log2 views per grid z and store their mean (shutter_tile).  All three of the plain batch variants only (no
+// STATS, no TILES, WPG 1, TORD 0: rt_internal.h trace_variant_built).
 // The options arrive as one variant word V (rt_internal.h VF_*, vf_cls = SMAX) and are read from it by name.
 template <int K, unsigned V>
 __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
-    constexpr bool STATS = (V & VF_STATS) != 0, PATH = (V & VF_PATH) != 0;
+    constexpr bool STATS = (V & VF_STATS) != 0, SHUTTER = (V & VF_SHUTTER) != 0;
+    constexpr int PATH = view_of(V);
     constexpr int SMAX = vf_cls_of(V), WPG = vf_wpg_of(V), TORD = vf_tord_of(V);
     constexpr int LDS_LEVELS = StackFor<K>::lds_levels;  // LdsStack slots, else unused
     __shared__ float2 stk_lv[LDS_LEVELS > 0 ? LDS_LEVELS * WG_THREADS * WPG : 1];
@@ -982,7 +1054,11 @@ __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
         t_rec[wave] = TileRec{in ? p.tile_cost + ((unsigned)tile_y * tiles_x + (unsigned)tile_x) : nullptr,
                               in ? (unsigned)__builtin_amdgcn_s_memrealtime() : 0u};
     }
-    const unsigned cnt = trace_tile_direct<K, V & VF_TILE>(p, tile_x, tile_y, lv, dv, tl);
+    if constexpr (SHUTTER) {
+        shutter_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int rec, int tx, int ty) { return trace_tile_direct<K, V & VF_TILE>(q, tx, ty, lv, dv, tl, rec); });
+        return;
+    }
+    const unsigned cnt = trace_tile_direct<K, V & VF_TILE>(p, tile_x, tile_y, lv, dv, tl).cnt;
     add_counters<STATS, PATH>(p, threadIdx.x & 63, cnt & CNT_REFL_MASK, cnt >> CNT_SHADOW_SHIFT, tl);
     if (TORD == 2 && (threadIdx.x & 63) == 0) {
         const TileRec r = t_rec[threadIdx.x >> 6];
@@ -1236,14 +1312,14 @@ __device__ __forceinline__ unsigned long long shadow_sphere_cull(const LaunchPar
 // Exact tests of the candidate spheres m (bits relative to `base`) of one bundle segment, in
 // ascending order (the reference's tie rules), for every lane (idle lanes trace a copy of an active
 // lane's ray).  A2OK: 2a finite-positive on every lane.
-template <bool PRIMARY, bool A2OK, bool PATH = false, typename T>
+template <bool PRIMARY, bool A2OK, int PATH = VIEW_ARGS, typename T>
 __device__ __forceinline__ void bundle_candidates(const LaunchParams& p, unsigned long long m, int base, f3 o, f3 d,
                                                   float a2, float a4, bool a2_ok, bool active, float& best_s,
-                                                  int& win_s, T& tl) {
+                                                  int& win_s, T& tl, int rec = 0) {
     auto test = [&](int i) -> float {
-        if (PRIMARY && ViewOf<PATH>{p}.prim_const()) {
+        if (PRIMARY && ViewOf<PATH>{p, rec}.prim_const()) {
             // o == camera: oc = cam - c and c = oc.oc - r^2 are per-frame constants (:614-619)
-            const PrimConst pc = ViewOf<PATH>{p}.pc()[i];
+            const PrimConst pc = ViewOf<PATH>{p, rec}.pc()[i];
             const float b = 2.0f * dot(mk(pc.ocx, pc.ocy, pc.ocz), d);
             const float disc = b * b - a4 * pc.c;
             return A2OK ? root_t1(b, disc, a2) : (a2_ok ? root_t1(b, disc, a2) : root_full(b, disc, a2));
@@ -1279,13 +1355,13 @@ __device__ __forceinline__ void bundle_candidates(const LaunchParams& p, unsigne
 // rule (:977, :987, :993) with the per-frame camera-relative constants; otherwise
 // TraceSecondaryRay's asymmetric rule (:804-806, :819-821, :825).
 // `planes`: the segment's nearest plane hit when the caller already has it (terminal segments).
-template <bool PRIMARY, bool PATH = false, typename T>
+template <bool PRIMARY, int PATH = VIEW_ARGS, typename T>
 __device__ __forceinline__ Hit nearest_bundle(const LaunchParams& p, f3 o, f3 d, bool active, T& tl,
-                                              unsigned long long pmask = 0, const Hit* planes = nullptr) {
+                                              unsigned long long pmask = 0, const Hit* planes = nullptr, int rec = 0) {
     const unsigned long long am = __builtin_amdgcn_ballot_w64(active);
     if (am == 0) return Hit{0.0f, HIT_NONE};
     // primary segment: the per-frame screen boxes replace the bundle cull
-    const bool use_box = PRIMARY && ViewOf<PATH>{p}.prim_const();
+    const bool use_box = PRIMARY && ViewOf<PATH>{p, rec}.prim_const();
     Bundle B{};
     if (!use_box) B = make_bundle(o, d, active, false);
     if (am != ~0ull) {  // idle lanes trace an exact copy of the first active lane's ray, so
@@ -1313,9 +1389,9 @@ __device__ __forceinline__ Hit nearest_bundle(const LaunchParams& p, f3 o, f3 d,
         // candidates in ascending order, selection by selects (take_*, no per-lane branches); the
         // root sequence is chosen once per wave (2a finite-positive on every lane: the usual case)
         if (__builtin_amdgcn_ballot_w64(!a2_ok) == 0)
-            bundle_candidates<PRIMARY, true, PATH>(p, m, base, o, d, a2, a4, a2_ok, active, best_s, win_s, tl);
+            bundle_candidates<PRIMARY, true, PATH>(p, m, base, o, d, a2, a4, a2_ok, active, best_s, win_s, tl, rec);
         else
-            bundle_candidates<PRIMARY, false, PATH>(p, m, base, o, d, a2, a4, a2_ok, active, best_s, win_s, tl);
+            bundle_candidates<PRIMARY, false, PATH>(p, m, base, o, d, a2, a4, a2_ok, active, best_s, win_s, tl, rec);
     }
     float best_p = __builtin_inff();
     int win_p = -1;
@@ -1631,15 +1707,15 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
 // Backward fold (converged call, all 64 lanes): level by level from the deepest, every recorded
 // hit is shaded; a mirror hit consumes the colour of the segment after it (levels 0..limit push
 // at most one record each, so K = limit + 1 records suffice).  Returns the lane's colour.
-template <bool GPOW, int MERGED, bool PATH = false, typename STK, typename T>
-__device__ __forceinline__ f3 fold_converged(const LaunchParams& p, STK& stk, f3 leaf, unsigned* cnt, T& tl) {
+template <bool GPOW, int MERGED, int PATH = VIEW_ARGS, typename STK, typename T>
+__device__ __forceinline__ f3 fold_converged(const LaunchParams& p, STK& stk, f3 leaf, unsigned* cnt, T& tl, int rec = 0) {
     f3 col = leaf;
     const int depth = stk.n;
     int level = (int)wave_max((float)depth);
     while (level-- > 0) {
         const bool act = level < depth;  // this lane's top record is at `level`
         float4 ra = make_float4(0.0f, 0.0f, 0.0f, 1.0f), rb = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
-        if (act) stk.template pop<PATH>(p, ra, rb);
+        if (act) stk.template pop<PATH>(p, ra, rb, rec);
         const unsigned long long am = __builtin_amdgcn_ballot_w64(act);
         if (am != ~0ull) {  // idle lanes shade a copy of the first active lane's record
             const int ref = __builtin_ctzll(am);
@@ -1664,9 +1740,10 @@ __device__ __forceinline__ f3 fold_converged(const LaunchParams& p, STK& stk, f3
 // BUNDLE kernel (scenes with >= CULL_MIN_SPHERES spheres): converged control flow so that
 // every segment and every light can form a wave bundle and cull the sphere list.
 template <int K, unsigned V, typename T>
-__device__ __forceinline__ unsigned trace_tile_bundle(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
-                                                      float* stk_dv, T& tl) {
-    constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = (V & VF_SS) != 0, PATH = (V & VF_PATH) != 0;
+__device__ __forceinline__ TileOut trace_tile_bundle(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
+                                                     float* stk_dv, T& tl, int rec = 0) {
+    constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = (V & VF_SS) != 0, SHUTTER = (V & VF_SHUTTER) != 0;
+    constexpr int PATH = view_of(V);
     constexpr int MERGED = vf_cls_of(V);
     const int lane = threadIdx.x & 63;
     const TilePixel tpx = tile_pixel<SS>(p, tile_x * TILE_W + (lane & 7), tile_y * TILE_H + (lane >> 3));
@@ -1674,7 +1751,7 @@ __device__ __forceinline__ unsigned trace_tile_bundle(const LaunchParams& p, int
     const bool valid = tpx.valid;
 
     unsigned cnt = 0;  // packed: reflected segments (bits 0-7) | shadow rays << CNT_SHADOW_SHIFT
-    const ViewOf<PATH> vw{p};
+    const ViewOf<PATH> vw{p, rec};
     const f3 cam = vw.cam();
     // TracePixel primary ray, :963-971 (no half-pixel offset)
     // per-column / per-row tables (see the direct kernel); lanes outside the frame read 0
@@ -1689,8 +1766,8 @@ __device__ __forceinline__ unsigned trace_tile_bundle(const LaunchParams& p, int
     stk.origin(d);
     f3 leaf = mk(0.0f, 0.0f, 0.0f);
     bool active = valid;
-    const unsigned long long pmask = vw.prim_const() ? prim_box_mask<PATH>(p, x, y) : 0;
-    Hit h = nearest_bundle<true, PATH>(p, o, d, active, tl, pmask);
+    const unsigned long long pmask = vw.prim_const() ? prim_box_mask<PATH>(p, x, y, rec) : 0;
+    Hit h = nearest_bundle<true, PATH>(p, o, d, active, tl, pmask, nullptr, rec);
     for (int count = 0;; ++count) {
         if (active) {
             const bool is_sphere = h.prim >= 0;
@@ -1734,10 +1811,10 @@ __device__ __forceinline__ unsigned trace_tile_bundle(const LaunchParams& p, int
         }
     }
 
-    const f3 col = fold_converged<GPOW, MERGED, PATH>(p, stk, leaf, &cnt, tl);
+    const f3 col = fold_converged<GPOW, MERGED, PATH>(p, stk, leaf, &cnt, tl, rec);
     const uint32_t px32 = (shift_channel(col.x) << 16) | (shift_channel(col.y) << 8) | shift_channel(col.z);
     if constexpr (TILES) encode_tile_fused(p, px32, valid);
-    else {
+    else if constexpr (!SHUTTER) {
         // the pixel's coordinates again, from the lane id (mbcnt) and the block id: cheaper than
         // keeping x, r, y and `valid` live through the walk and the fold (64-VGPR cap: they were
         // the values spilled to scratch once the merged shadow pass raised the peak)
@@ -1746,7 +1823,7 @@ __device__ __forceinline__ unsigned trace_tile_bundle(const LaunchParams& p, int
         if constexpr (SS) resolve_tile(p, q.r, q.y, q.x, q.valid, px32);
         else if (q.valid) store_pixel(p, q.r, q.y, q.x, px32);
     }
-    return cnt;
+    return TileOut{cnt, px32};  // (lanes outside the frame: a value that is never stored)
 }
 
 // Occupancy: a wave's SGPRs count against a per-SIMD file of ~800 (waves per SIMD <=
@@ -1759,7 +1836,8 @@ __device__ __forceinline__ unsigned trace_tile_bundle(const LaunchParams& p, int
 // 2-D grid, 2 = natural and every wave records its duration in tile_cost).  V: the variant word (vf_cls = MERGED).
 template <int K, unsigned V>
 __device__ __forceinline__ void bundle_kernel_body(const LaunchParams& p) {
-    constexpr bool STATS = (V & VF_STATS) != 0, PATH = (V & VF_PATH) != 0;
+    constexpr bool STATS = (V & VF_STATS) != 0, SHUTTER = (V & VF_SHUTTER) != 0;
+    constexpr int PATH = view_of(V);
     constexpr int TORD = vf_tord_of(V);
     constexpr int LDS_LEVELS = StackFor<K>::lds_levels;  // LdsStack slots, else unused
     __shared__ float2 stk_lv[LDS_LEVELS > 0 ? LDS_LEVELS * WG_THREADS : 1];
@@ -1783,7 +1861,11 @@ __device__ __forceinline__ void bundle_kernel_body(const LaunchParams& p) {
     if (TORD == 2 && (threadIdx.x & 63) == 0)  // (a batch launch's frame 0 records; the others store nothing)
         t_rec[0] = TileRec{blockIdx.z == (unsigned)p.copy_z ? p.tile_cost + (blockIdx.y * gridDim.x + blockIdx.x) : nullptr,
                            (unsigned)__builtin_amdgcn_s_memrealtime()};
-    const unsigned cnt = trace_tile_bundle<K, V & VF_TILE>(p, tile_x, tile_y, stk_lv, stk_dv, tl);
+    if constexpr (SHUTTER) {
+        shutter_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int rec, int tx, int ty) { return trace_tile_bundle<K, V & VF_TILE>(q, tx, ty, stk_lv, stk_dv, tl, rec); });
+        return;
+    }
+    const unsigned cnt = trace_tile_bundle<K, V & VF_TILE>(p, tile_x, tile_y, stk_lv, stk_dv, tl).cnt;
     add_counters<STATS, PATH>(p, threadIdx.x & 63, cnt & CNT_REFL_MASK, cnt >> CNT_SHADOW_SHIFT, tl);
     if (TORD == 2 && (threadIdx.x & 63) == 0 && t_rec[0].slot != nullptr)
         *t_rec[0].slot = (unsigned)__builtin_amdgcn_s_memrealtime() - t_rec[0].t0;
@@ -1955,7 +2037,7 @@ int launch_trace(const LaunchParams& p, bool generic_pow, bool stats, void* stre
     auto leaf = [&](auto consts) { return launch_built(consts, p, grid, block, (hipStream_t)stream); };
     // (pick_trace_variant returns built descriptors only: an unbuilt one is an error, not a kernel)
     if (!peel(leaf, Vals<>{}, v.family, Vals<TV_DIRECT, TV_BUNDLE>{}, v.gpow, Vals<0, 1>{}, v.mode,
-              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
+              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
               Vals<1, 2, 4, 6, 8, 64>{}, v.wpg, Vals<1, SINGLE_WPG>{}, v.tord, Vals<0, 1, 2>{}))
         return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();

@@ -6,8 +6,14 @@
 // words of 16-bit fields -- {R, B} and {G} -- so that a channel's sum of up to 64 samples (64 * 255 =
 // 16,320 < 2^14) never carries into its neighbour; sums of unpacked samples are plain 32-bit adds (the
 // kernel's cross-lane steps), and the rounding works on both fields of a word at once.
+//
+// The camera-path shutter (rt_render_shutter_bands) averages m = 1 << t sub-frames of one pixel, m up to
+// RT_MAX_SHUTTER = 256, with the same unpacked sums: a field then holds 256 * 255 + 128 = 65,408 < 2^16, rounding
+// term included, so resolve_round_n needs no wider word.
 #pragma once
 #include <stdint.h>
+
+#include "../../include/raytracer_hip.h"
 
 #if defined(__HIPCC__)
 #define RT_RESOLVE_FN __host__ __device__ inline
@@ -32,6 +38,16 @@ RT_RESOLVE_FN uint32_t resolve_round(ResolveSum sum, int s) {
     const uint32_t half = (1u << sh) >> 1;  // k*k/2 (s = 0: 0, the sample itself)
     const uint32_t rb = ((sum.rb + (half | (half << 16))) >> sh) & 0x00ff00ffu;  // (R's low bits fall into B's field: masked)
     const uint32_t g = ((sum.g + half) >> sh) & 0xffu;
+    return rb | (g << 8);
+}
+
+// The sum of 1 << t unpacked sub-frame pixels (t = 0 .. 8) -> the output pixel 0x00RRGGBB, the round-half-up mean
+// per channel: (sum + m / 2) >> t.
+static_assert(RT_MAX_SHUTTER * 255 + RT_MAX_SHUTTER / 2 < 65536, "a channel's shutter sum and its rounding term fit a 16-bit field");
+RT_RESOLVE_FN uint32_t resolve_round_n(ResolveSum sum, int t) {
+    const uint32_t half = (1u << t) >> 1;  // m / 2 (t = 0: 0, the pixel itself)
+    const uint32_t rb = ((sum.rb + (half | (half << 16))) >> t) & 0x00ff00ffu;  // (R's low bits fall into B's field: masked)
+    const uint32_t g = ((sum.g + half) >> t) & 0xffu;
     return rb | (g << 8);
 }
 

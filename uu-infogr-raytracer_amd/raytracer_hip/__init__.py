@@ -208,6 +208,34 @@ class Context:
         self._check(self.lib.rt_render_path(self.ptr, width, height, cams, n, out.ctypes.data))
         return out.reshape(n, height, width)
 
+    def render_shutter_bands(self, width: int, height: int, cameras, shutter: int, band_rows: int, band_first: int,
+                             band_step: int, d_ptr: int, frame_stride_bytes: int, fmt: int = abi.RT_BANDS_INT32,
+                             stream: int = 0) -> int:
+        """len(cameras) / shutter output frames in one launch, frame f the in-kernel round-half-up mean of the
+        frames seen from cameras[f * shutter : (f + 1) * shutter] (path.subframes makes such a list), these bands
+        of it at d_ptr + f * frame_stride_bytes (rt_render_shutter_bands).  shutter: a power of two up to 256."""
+        cams = path.as_array(cameras)
+        if shutter < 1 or len(cams) % shutter:
+            raise ValueError(f"{len(cams)} cameras are no multiple of the shutter {shutter}")
+        nb = C.c_int(0)
+        self._check(self.lib.rt_render_shutter_bands(self.ptr, width, height, cams, len(cams) // shutter, shutter,
+                                                     band_rows, band_first, band_step, C.c_void_p(d_ptr),
+                                                     frame_stride_bytes, fmt, C.c_void_p(stream), C.byref(nb)))
+        return nb.value
+
+    def render_shutter(self, cameras, width: int, height: int, shutter: int, out: np.ndarray | None = None) -> np.ndarray:
+        """Whole frames of a camera path with a shutter into host memory, [len(cameras) / shutter, height, width]
+        (rt_render_shutter; synchronous): frame f is the mean of its `shutter` sub-frame cameras."""
+        cams = path.as_array(cameras)
+        if shutter < 1 or len(cams) % shutter:
+            raise ValueError(f"{len(cams)} cameras are no multiple of the shutter {shutter}")
+        n = len(cams) // shutter
+        if out is None:
+            out = np.empty((n, height, width), dtype=np.int32)
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.size == n * width * height
+        self._check(self.lib.rt_render_shutter(self.ptr, width, height, cams, n, shutter, out.ctypes.data))
+        return out.reshape(n, height, width)
+
     def scatter_gathered(self, width: int, height: int, band_rows: int, world: int, d_gathered: int,
                          rank_stride: int, d_frame: int, fmt: int = abi.RT_BANDS_RGB24, stream: int = 0):
         """Reassemble all ranks' band sets (rank r's at d_gathered + r * rank_stride) into d_frame."""

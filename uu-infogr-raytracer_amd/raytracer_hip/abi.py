@@ -20,6 +20,7 @@ RT_CREATE_RCCL_GATHER = 1
 RT_CREATE_SHARED_DEVICE = 2
 RT_MAX_WORKERS = 64
 RT_MAX_PATH_FRAMES = 65535  # rt_render_path_bands / rt_render_path: frames per call (grid z)
+RT_MAX_SHUTTER = 256  # rt_render_shutter_bands / rt_render_shutter: sub-frame cameras per output frame
 RT_BANDS_INT32, RT_BANDS_RGB24, RT_BANDS_FRAME = 0, 1, 2
 RT_OK = 0
 RT_ERR_INVALID_ARG = -1
@@ -138,6 +139,10 @@ EXPORTS = [
     ("rt_render_path_bands", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     ("rt_render_path", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_void_p]),
+    ("rt_render_shutter_bands", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                          C.POINTER(C.c_int)]),
+    ("rt_render_shutter", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_void_p]),
     ("rt_scatter_gathered", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                       C.c_int, C.c_void_p, C.c_void_p]),
     ("rt_wire_layout_of", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(rt_wire_layout)]),
