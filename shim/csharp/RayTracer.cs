@@ -47,6 +47,8 @@ internal static class Native {
     [DllImport(Lib)] internal static extern int rt_dispatch_order(IntPtr ctx, out int order);
     [DllImport(Lib)] internal static extern int rt_set_counting(IntPtr ctx, int on);  // ABI 10
     [DllImport(Lib)] internal static extern int rt_set_supersampling(IntPtr ctx, int k);  // ABI 10 addition
+    [DllImport(Lib)] internal static extern int rt_set_adaptive_sampling(IntPtr ctx, int threshold);  // ABI 10 addition
+    [DllImport(Lib)] internal static extern int rt_get_adaptive_sampling(IntPtr ctx, out int threshold);
 
     internal static void Check(int rc, IntPtr ctx) {
         if (rc != 0) throw new InvalidOperationException($"libraytracer_hip error {rc}: {Marshal.PtrToStringAnsi(rt_last_error(ctx))}");
@@ -73,6 +75,10 @@ internal sealed class RayTracer : IDisposable {
         // RT_SAMPLES=2|4|8: k x k supersampling resolved on the GPU (the frame handed to the window keeps its size)
         int samples = int.TryParse(Environment.GetEnvironmentVariable("RT_SAMPLES"), out int k) ? k : 1;
         Native.Check(Native.rt_set_supersampling(_ctx, samples), _ctx);
+        // RT_ADAPTIVE=1..256 (with RT_SAMPLES > 1): only the 8x8 tiles whose neighbouring pixels differ by that much in
+        // a channel are supersampled; 0 or unset: every pixel
+        int adaptive = int.TryParse(Environment.GetEnvironmentVariable("RT_ADAPTIVE"), out int t) ? t : 0;
+        Native.Check(Native.rt_set_adaptive_sampling(_ctx, adaptive), _ctx);
         // the hard-coded scene of RayTracer.cs:441-469
         static Native.Vec3 V(float x, float y, float z) => new(x, y, z);
         static Native.Material M(Native.Vec3 kd, Native.Vec3 ka, Native.Vec3 ks, float n, Native.Vec3 km) =>

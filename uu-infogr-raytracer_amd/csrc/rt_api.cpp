@@ -279,6 +279,7 @@ struct rt_ctx {
     int view_w = 0, view_h = 0, view_rows = 0;
     int view_height = 0;  // rt_set_view_height: the view's height (0: each render's own frame height)
     int ss_log2 = 0;      // rt_set_supersampling: log2 of the factor k (0: off)
+    int adapt_thr = 0;    // rt_set_adaptive_sampling: the threshold T in 1..256 (0: off); in effect while ss_log2 > 0
     LaunchParams view_lp{};
 };
 
@@ -941,7 +942,8 @@ struct EncTarget {
 // The tail of trace_bands and trace_path: lp launched on `stream` as one of device d's sampled-timing traces
 // (`what` names the caller in the error text), the launch counted and, while the context counts
 // (rt_set_counting), the pixels of rows < H in the nb launched bands (first, step) of n_frames frames; ss:
-// supersampling, so samples.  Nothing but the launch lies between the timing events; a caller that probes the
+// supersampling, so samples -- but one per pixel in an adaptive launch (lp.adapt_thr > 0), whose waves count the
+// samples they trace beyond that on the device (CNT_EXTRA_PRIMARY, rt_get_stats).  Nothing but the launch lies between the timing events; a caller that probes the
 // dispatch order brackets the whole call with order_begin / order_end.
 int launch_counted(rt_ctx* ctx, Device& d, hipStream_t stream, const LaunchParams& lp, const char* what, int W, int H,
                    int band_rows, int first, int step, int nb, int n_frames, int ss) {
@@ -953,11 +955,23 @@ int launch_counted(rt_ctx* ctx, Device& d, hipStream_t stream, const LaunchParam
     d.stream = saved;
     if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString((hipError_t)e));
     ctx->launches++;
+    if (lp.adapt_thr > 0) ss = 0;
     for (int k = 0; k < nb && ctx->counting; ++k) {
         const long long y0 = (long long)(first + k * step) * band_rows;
         ctx->prim_rays += ((uint64_t)std::min<long long>(band_rows, (long long)H - y0) * (uint64_t)W * (uint64_t)n_frames)
                           << (2 * ss);
     }
+    return RT_OK;
+}
+
+// Adaptive sampling in effect (rt_set_adaptive_sampling with k > 1): the 8x8 tiles of a band render sit on the
+// frame's 8-row grid (rt_internal.h adaptive_band_ok; the library's own 8-row bands and chunks do).  The band
+// renders ask before they touch a device, trace_bands before every launch.
+int check_adaptive_bands(rt_ctx* ctx, int band_rows, int H) {
+    if (ctx->ss_log2 > 0 && ctx->adapt_thr > 0 && !adaptive_band_ok(band_rows, H))
+        return fail(ctx, RT_ERR_UNSUPPORTED,
+                    "adaptive sampling needs bands of a multiple of 8 rows, or one band of the whole frame (band_rows %d, height %d)",
+                    band_rows, H);
     return RT_OK;
 }
 
@@ -984,6 +998,8 @@ int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, const TraceReq& q) {
     const EncTarget* enc = q.enc;
     const int ss = ctx->ss_log2;
     if (ss > 0 && enc) return fail(ctx, RT_ERR_UNSUPPORTED, "the fused tile encoder does not supersample");
+    const int thr = ss > 0 ? ctx->adapt_thr : 0;
+    RT_TRY(check_adaptive_bands(ctx, band_rows, H));
     LaunchParams lp;
     std::memset(&lp, 0, sizeof lp);
     RT_TRY(view_params(ctx, W << ss, H << ss, lp, ss));
@@ -996,6 +1012,7 @@ int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, const TraceReq& q) {
         lp.band_rows = std::min(band_rows, H) << ss;
         lp.local_rows = nb * lp.band_rows;
         lp.ss_log2 = ss;
+        lp.adapt_thr = thr;
     } else {
         lp.band_rows = band_rows;
         lp.local_rows = nb * band_rows;
@@ -1087,6 +1104,7 @@ int32_t* mapped_host(const rt_ctx* ctx, int g, void* host, size_t bytes) {
 // band) -- balanced however the scene's cost is spread over the rows (the top ~45 % of C2 is sky) --
 // packed band after band, and hands them to the caller's frame itself.
 constexpr int TICK_BAND_ROWS = 8;
+static_assert(TICK_BAND_ROWS % 8 == 0, "the Tick's bands hold whole tiles of an adaptive launch (adaptive_band_ok)");
 struct Share {
     int band_rows, first, step, nb;  // bands (first, step) of band_rows rows, nb of them
     size_t words;                    // int32 of the packed band set inside the frame (a cut last band)
@@ -1837,6 +1855,20 @@ int rt_get_supersampling(const rt_ctx* ctx, int* out_k) {
     return RT_OK;
 }
 
+int rt_set_adaptive_sampling(rt_ctx* ctx, int threshold) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_set_adaptive_sampling: NULL context");
+    if (threshold < 0 || threshold > 256)
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_set_adaptive_sampling: threshold %d is not in 0..256", threshold);
+    ctx->adapt_thr = threshold;
+    return RT_OK;
+}
+
+int rt_get_adaptive_sampling(const rt_ctx* ctx, int* out_threshold) {
+    if (!ctx || !out_threshold) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_get_adaptive_sampling: NULL argument");
+    *out_threshold = ctx->adapt_thr;
+    return RT_OK;
+}
+
 int rt_set_camera(rt_ctx* ctx, const rt_camera* camera) {
     if (!ctx || !camera) return fail(ctx, RT_ERR_INVALID_ARG, "rt_set_camera: NULL argument");
     ctx->cam = *camera;
@@ -1961,6 +1993,7 @@ int rt_render_bands_ex(rt_ctx* ctx, int width, int height, int band_rows, int ba
                        int format, void* hip_stream, int* out_n_bands) {
     RT_TRY(check_ctx(ctx, width, height));
     RT_TRY(check_band_args(ctx, "rt_render_bands", band_rows, band_first, band_step, d_out, format));
+    RT_TRY(check_adaptive_bands(ctx, band_rows, height));
     if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_bands needs a single-GPU context");
     Device& d = ctx->dev[0];
     DeviceGuard guard(d.id);
@@ -1977,6 +2010,7 @@ int rt_render_bands_batch(rt_ctx* ctx, int width, int height, int band_rows, int
                           int* out_n_bands) {
     RT_TRY(check_ctx(ctx, width, height));
     RT_TRY(check_band_args(ctx, "rt_render_bands_batch", band_rows, band_first, band_step, d_out, format));
+    RT_TRY(check_adaptive_bands(ctx, band_rows, height));
     if (n_frames <= 0 || n_frames > 65535)
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_bands_batch: bad band arguments");
     if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_bands_batch needs a single-GPU context");
@@ -2748,12 +2782,13 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out) {
     }
     out->frames = ctx->frames;
     out->pixels = ctx->pixels;
-    out->primary_rays = ctx->prim_rays;
+    // (adaptive launches: one primary ray per pixel counted on the host, the refined tiles' other samples by the waves)
+    out->primary_rays = ctx->prim_rays + c[CNT_EXTRA_PRIMARY];
     out->reflect_rays = c[CNT_REFLECT];
     out->shadow_rays = c[CNT_SHADOW];
     const uint64_t S = (uint64_t)ctx->layout.S, P = (uint64_t)ctx->layout.P;
-    out->sphere_tests = (ctx->prim_rays + c[1] + c[2]) * S;
-    out->plane_tests = (ctx->prim_rays + c[1]) * P;
+    out->sphere_tests = (out->primary_rays + c[1] + c[2]) * S;
+    out->plane_tests = (out->primary_rays + c[1]) * P;
     out->launches = ctx->launches;
     out->kernel_ms = ctx->kernel_ms;
     out->last_kernel_ms = ctx->last_kernel_ms;

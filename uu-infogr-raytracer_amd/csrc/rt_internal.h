@@ -128,6 +128,9 @@ constexpr int COUNTER_SLOTS = 256;
 constexpr int COUNTER_STRIDE = 8;
 constexpr int COUNTER_WORDS = COUNTER_SLOTS * COUNTER_STRIDE;
 enum : int { CNT_REFLECT = 1, CNT_SHADOW = 2, CNT_SHADOW_RUN = 3, CNT_SPHERE_RUN = 4, CNT_PLANE_RUN = 5 };
+// Adaptive supersampling (rt_set_adaptive_sampling): the samples its waves traced beyond one per rendered pixel,
+// k^2 - 1 per valid pixel of every refined tile -- the part of primary_rays the host cannot know (rt_get_stats).
+enum : int { CNT_EXTRA_PRIMARY = 0 };
 
 // Camera-relative sphere constants of the primary segment (origin = camera position for
 // every pixel): oc = cam - center and c = Dot(oc, oc) - r^2 of IntersectsSphere
@@ -259,6 +262,12 @@ struct LaunchParams {
     // records, sub-frame s of grid z at views[z << t | s], and a wave traces its tile once per sub-frame and stores
     // the round-half-up mean (rt_resolve.h resolve_round_n).  Last: no other field moves.
     int shutter_log2;
+    // Adaptive supersampling (rt_set_adaptive_sampling, the ADAPT instantiations): the threshold T in 1..256 of a
+    // launch with ss_log2 > 0, 0 = every block is supersampled (the SS instantiations).  With it set a lane is an
+    // output pixel, the wave traces sample (0, 0) of its 8x8 output tile, and the other k^2 - 1 samples only when
+    // two 4-adjacent pixels of the tile differ by >= T in a channel (rt_kernel.hip adaptive_tile); the grid is in
+    // output tiles.  Last: no other field moves.
+    int adapt_thr;
 };
 constexpr int MIRROR_BOX_PLANES = 2;
 // Tiles per workgroup of the direct kernel's single-frame launches (8: +2.5 % on C2,
@@ -282,8 +291,9 @@ constexpr int DIRECT_SMAX = 8;
 enum : int { TV_DIRECT = 0, TV_BUNDLE = 1 };
 // PLAIN: pixels to `out`.  STATS: as PLAIN, and the diagnostic tallies of the executed work.  TILES: out_fmt
 // OUT_TILES, the fused tile encoder.  SS: the supersampling epilogue.  PATH: one DevView per grid z.  SHUTTER: a
-// PATH launch whose waves average 1 << shutter_log2 DevViews per grid z.
-enum : int { TM_PLAIN = 0, TM_STATS = 1, TM_TILES = 2, TM_SS = 3, TM_PATH = 4, TM_SHUTTER = 5 };
+// PATH launch whose waves average 1 << shutter_log2 DevViews per grid z.  ADAPT: supersampling decided per output
+// tile (LaunchParams::adapt_thr).
+enum : int { TM_PLAIN = 0, TM_STATS = 1, TM_TILES = 2, TM_SS = 3, TM_PATH = 4, TM_SHUTTER = 5, TM_ADAPT = 6 };
 struct TraceVariant {
     int family;  // TV_*
     int gpow;    // some material needs the f64 Math.Pow path: the entry points without the register caps
@@ -294,7 +304,7 @@ struct TraceVariant {
     int tord;    // 0: tiles in grid order (row_order / col_major), 1: tile_order, 2: as 0 and tile_cost recorded
 };
 
-enum : unsigned { VF_GPOW = 1u, VF_STATS = 2u, VF_TILES = 4u, VF_SS = 8u, VF_PATH = 16u, VF_SHUTTER = 32u };
+enum : unsigned { VF_GPOW = 1u, VF_STATS = 2u, VF_TILES = 4u, VF_SS = 8u, VF_PATH = 16u, VF_SHUTTER = 32u, VF_ADAPT = 64u };
 constexpr unsigned vf_cls(int c) { return (unsigned)c << 8; }
 constexpr unsigned vf_wpg(int w) { return (unsigned)w << 12; }
 constexpr unsigned vf_tord(int t) { return (unsigned)t << 16; }
@@ -305,7 +315,7 @@ static_assert(DIRECT_SMAX < 16 && SINGLE_WPG < 16, "the variant word's 4-bit fie
 constexpr unsigned variant_word(const TraceVariant& v) {
     return (v.gpow ? VF_GPOW : 0u) | (v.mode == TM_STATS ? VF_STATS : 0u) | (v.mode == TM_TILES ? VF_TILES : 0u) |
            (v.mode == TM_SS ? VF_SS : 0u) | (v.mode == TM_PATH ? VF_PATH : 0u) |
-           (v.mode == TM_SHUTTER ? VF_SHUTTER : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
+           (v.mode == TM_SHUTTER ? VF_SHUTTER : 0u) | (v.mode == TM_ADAPT ? VF_ADAPT : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
 }
 
 // The bundle family's shadow pass by scene: 0 = per light (also every scene of the direct family), 1 = the
@@ -316,10 +326,14 @@ inline int merged_class(int S, int L, bool lights_a2_ok) {
     return lights_a2_ok ? 2 : 1;
 }
 
-// The instantiations that exist (444): every mode, depth and class of both families at one tile per workgroup
-// in grid order (SHUTTER among them, under PATH's conditions: 60 of its own); the direct kernel's lone-frame
-// workgroups of SINGLE_WPG tiles in each tile order (PLAIN only); the all-lights-ok merged bundle kernel's tile
-// orders (PLAIN, no GPOW).
+// The band rule of an adaptive launch (rt_set_adaptive_sampling with k > 1): its 8x8 tiles are tiles of the frame's
+// 8-row grid when the bands are multiples of 8 output rows, or when one band covers the frame.
+inline bool adaptive_band_ok(int band_rows, int H) { return band_rows % 8 == 0 || band_rows >= H; }
+
+// The instantiations that exist (504): every mode, depth and class of both families at one tile per workgroup
+// in grid order (SHUTTER among them, under PATH's conditions, and ADAPT, under SS's: 60 of their own each); the
+// direct kernel's lone-frame workgroups of SINGLE_WPG tiles in each tile order (PLAIN only); the all-lights-ok
+// merged bundle kernel's tile orders (PLAIN, no GPOW).
 constexpr bool trace_variant_built(const TraceVariant& v) {
     const bool plain = v.mode == TM_PLAIN;
     if (v.family == TV_DIRECT)
@@ -337,8 +351,8 @@ inline bool pick_trace_variant(const LaunchParams& p, bool generic_pow, bool sta
             return false;
         v->mode = p.shutter_log2 > 0 ? TM_SHUTTER : TM_PATH;
     } else if (p.ss_log2 > 0) {
-        if (p.ss_log2 > 3 || tiles || stats || ordered) return false;
-        v->mode = TM_SS;
+        if (p.ss_log2 > 3 || tiles || stats || ordered || p.adapt_thr < 0 || p.adapt_thr > 256) return false;
+        v->mode = p.adapt_thr > 0 ? TM_ADAPT : TM_SS;
     } else {
         v->mode = tiles ? TM_TILES : stats ? TM_STATS : TM_PLAIN;  // (the fused encoder never tallies)
     }

@@ -751,6 +751,15 @@ __device__ __forceinline__ TilePixel tile_pixel(const LaunchParams& p, int x, in
     t.lx = t.valid ? lx : 0.0f, t.ly = t.valid ? ly : 0.0f;
     return t;
 }
+// ADAPT (adaptive supersampling, adaptive_tile): the wave's tile is 8x8 output pixels, lane `lane` is pixel (rx, ry) =
+// (lane & 7, lane >> 3) of it and traces sample (i, j) = (pass & (k - 1), pass >> ss_log2) of its pixel's k x k
+// block, k = 1 << ss_log2: column (x << ss_log2) | i of local sample row (r << ss_log2) | j of the sample frame
+// LaunchParams describes; `pass` is wave-uniform.  The mapping stays monotonic in the lane, so lanes 0 and 63 still
+// hold the wave's extremes (box_mask).
+__device__ __forceinline__ TilePixel sample_pixel(const LaunchParams& p, int tile_x, int tile_y, int lane, int pass) {
+    const int x = tile_x * TILE_W + (lane & 7), r = tile_y * TILE_H + (lane >> 3), s2 = p.ss_log2;
+    return tile_pixel<true>(p, (x << s2) | (pass & ((1 << s2) - 1)), (r << s2) | (pass >> s2));
+}
 
 // Sphere part of a nearest-hit search for the active lanes.  PRIMARY with p.prim_const: the
 // per-frame camera-relative constants and the wave's screen-box candidates (pmask); otherwise
@@ -862,14 +871,17 @@ struct TileOut {
 };
 
 // DIRECT path, one 8x8 tile: each lane walks its own chain with per-lane (divergent) control
-// flow.  rec: the sub-frame's view record (SHUTTER only, wave-uniform; see ViewOf).
+// flow.  rec: the sub-frame's view record (SHUTTER, wave-uniform; see ViewOf), or the sample pass (ADAPT, wave-uniform;
+// sample_pixel) -- the ADAPT kernels have the one view of the launch parameters and ViewOf never reads it.
 template <int K, unsigned V, typename T>
 __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
                                                      float* stk_dv, T& tl, int rec = 0) {
     constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = (V & VF_SS) != 0, SHUTTER = (V & VF_SHUTTER) != 0;
+    constexpr bool ADAPT = (V & VF_ADAPT) != 0;
     constexpr int PATH = view_of(V);
     const int lane = threadIdx.x & 63;
-    const TilePixel tpx = tile_pixel<SS>(p, tile_x * TILE_W + (lane & 7), tile_y * TILE_H + (lane >> 3));
+    const TilePixel tpx = ADAPT ? sample_pixel(p, tile_x, tile_y, lane, rec)
+                                : tile_pixel<SS>(p, tile_x * TILE_W + (lane & 7), tile_y * TILE_H + (lane >> 3));
     const int x = tpx.x, r = tpx.r, y = tpx.y;
     const bool valid = tpx.valid;
     const ViewOf<PATH> vw{p, rec};
@@ -938,7 +950,7 @@ __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int 
                                            mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl);
         }
         px32 = (shift_channel(col.x) << 16) | (shift_channel(col.y) << 8) | shift_channel(col.z);
-        if constexpr (!TILES && !SS && !SHUTTER) store_pixel(p, r, y, x, px32);
+        if constexpr (!TILES && !SS && !SHUTTER && !ADAPT) store_pixel(p, r, y, x, px32);
     }
     if constexpr (TILES) encode_tile_fused(p, px32, valid);
     if constexpr (SS) resolve_tile(p, r, y, x, valid, px32);
@@ -996,6 +1008,83 @@ __device__ __forceinline__ void shutter_tile(const LaunchParams& p, int tile_x, 
     }
 }
 
+// ADAPT (rt_set_adaptive_sampling with supersampling on): the wave's tile is 8x8 output pixels, a lane is one of
+// them, and `trace(p, pass, tile_x, tile_y)` traces sample pass = j k + i of every pixel's k x k block (sample_pixel),
+// k = 1 << ss_log2.  Pass 0 is sample (0, 0), which is bit for bit the pixel of the frame without supersampling
+// (DESIGN.md section 4), so the decision costs no trace of its own: after pass 0 the wave looks for two 4-adjacent
+// valid pixels of the tile that differ by >= adapt_thr in a channel (rt_resolve.h adapt_differs) -- each lane
+// against the lane at -1 (rx >= 1) and at -8 (ry >= 1), by DPP / bpermute as in encode_tile_fused, one ballot --
+// and leaves the loop when there is none (a flat tile: the sum is pass 0's pixel itself).  Otherwise the remaining
+// k^2 - 1 passes add to the running sums (16-bit fields: at most 64 samples) and the tile stores the round-half-up
+// mean.  The valid lanes of a tile form a rectangle that starts at its lane 0 (x < W, r < local_rows and y < H are
+// monotonic, and a tile never straddles a band: bands are multiples of 8 output rows or the launch has one), so
+// a valid lane's neighbours at -1 and -8 are valid: the lane's own validity is the pair's.
+// The loop obeys what shutter_tile found: no write to global memory inside it (ray counts reduced per pass into
+// scalars, added once after it, the wave's extra samples with them), and the tile position and the kernarg address
+// pass through the empty asm tied to the loop counter, so that nothing is hoisted and held across the traces.  It
+// also carries as little as it can (see below): with the factor, the threshold, the pass count and the counting
+// flag held in SGPRs across the traces the K <= 8 bundle kernels of class 0 spilled a VGPR to scratch.
+// Counting follows add_counters: frame 0 of a batch (behind a copy slice) counts for all its frames.
+template <typename F>
+__device__ __forceinline__ void adaptive_tile(const LaunchParams& p, int tile_x, int tile_y, F trace) {
+    // Carried across a trace: the pass counter, the sums (two VGPRs) and the wave's ray totals (three SGPRs: at
+    // most 64 lanes x 64 segments x 64 passes reflected segments fit 32 bits).  Everything else -- the factor, the
+    // threshold, whether the wave counts -- is read again from the launch parameters where it is used, so that
+    // nothing more competes with the trace for the 80 SGPRs; the loop ends at pass 0 on a flat tile, so s != 0
+    // after it says "refined".
+    ResolveSum acc{0u, 0u};
+    unsigned n_refl = 0;
+    unsigned long long n_shadow = 0;
+    int s = 0;
+#pragma unroll 1
+    for (;; ++s) {  // wave-uniform
+        int tx = tile_x, ty = tile_y;
+        asm("" : "+s"(tx), "+s"(ty) : "s"(s));
+        const __attribute__((address_space(4))) LaunchParams* kp =
+            (const __attribute__((address_space(4))) LaunchParams*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm("" : "+s"(kp) : "s"(s));
+        const LaunchParams& q = *(const LaunchParams*)kp;
+        const TileOut o = trace(q, s, tx, ty);
+        acc = resolve_add(acc, resolve_unpack(o.px32));
+        if (q.counters != nullptr && blockIdx.z == (unsigned)q.copy_z) {  // wave-uniform
+            n_refl += wave_count(o.cnt & CNT_REFL_MASK);
+            n_shadow += wave_count(o.cnt >> CNT_SHADOW_SHIFT);
+        }
+        if (s == 0) {  // the decision, on the frame without supersampling
+            const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            const bool valid = sample_pixel(q, tx, ty, ln, 0).valid;
+            const int thr = q.adapt_thr;
+            const uint32_t v = o.px32 & 0xffffffu;
+            const uint32_t left = row_shr<1>(v);                        // lane - 1: the same row for rx >= 1
+            const uint32_t above = (uint32_t)__shfl_up((int)v, 8, 64);  // lane - 8: the row above
+            const bool differs = valid && (((ln & 7) != 0 && adapt_differs(v, left, thr)) ||
+                                           ((ln >> 3) != 0 && adapt_differs(v, above, thr)));
+            if (__builtin_amdgcn_ballot_w64(differs) == 0) break;  // flat
+        }
+        if (s + 1 >= 1 << (2 * q.ss_log2)) break;
+    }
+    const int s2 = p.ss_log2;
+    const bool refined = s != 0;
+    const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const TilePixel t = sample_pixel(p, tile_x, tile_y, ln, 0);  // the pixel's sample (0, 0)
+    if (t.valid)  // (output coordinates: r and y agree modulo k, bands are multiples of k sample rows)
+        store_at(p, (size_t)((p.out_fmt == 2 ? t.y : t.r) >> s2) * (size_t)(p.W >> s2) + (size_t)(t.x >> s2),
+                 resolve_round(acc, refined ? s2 : 0));
+    if (p.counters != nullptr && blockIdx.z == (unsigned)p.copy_z) {  // wave-uniform
+        // the samples beyond one per pixel: k^2 - 1 per valid pixel of a refined tile
+        const unsigned long long n_extra = refined ? (unsigned long long)((1 << (2 * s2)) - 1) *
+                                                         (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(t.valid))
+                                                   : 0ull;
+        if (ln == 0) {
+            const unsigned long long nf = p.n_frames > 1 ? (unsigned long long)p.n_frames : 1ull;
+            unsigned long long* c = &p.counters[((blockIdx.y * gridDim.x + blockIdx.x) % COUNTER_SLOTS) * COUNTER_STRIDE];
+            if (n_refl) atomicAdd(c + CNT_REFLECT, n_refl * nf);
+            if (n_shadow) atomicAdd(c + CNT_SHADOW, n_shadow * nf);
+            if (n_extra) atomicAdd(c + CNT_EXTRA_PRIMARY, n_extra * nf);
+        }
+    }
+}
+
 // DIRECT kernel (scenes with < CULL_MIN_SPHERES spheres).
 // STATS: the diagnostic build that also tallies the work actually executed (not timed).
 // TILES: out_fmt OUT_TILES (the fused encoder: its own instantiation, so that the others keep their
@@ -1010,8 +1099,9 @@ __device__ __forceinline__ void shutter_tile(const LaunchParams& p, int tile_x, 
 // one-frame launch 2 % and 10 % (C2 19.9 -> 20.3 / 22.4 us, profiles/ab/r05_tile_order.txt).
 // SS: the supersampling epilogue (resolve_tile) in place of the pixel stores.  PATH: frame z of the grid takes its
 // view from LaunchParams::views (one DevView per grid z).  SHUTTER: a PATH launch whose waves trace 1 <<
-// shutter_log2 views per grid z and store their mean (shutter_tile).  All three of the plain batch variants only (no
-// STATS, no TILES, WPG 1, TORD 0: rt_internal.h trace_variant_built).
+// shutter_log2 views per grid z and store their mean (shutter_tile).  ADAPT: supersampling whose waves decide per
+// 8x8 output tile whether to trace more than one sample per pixel (adaptive_tile).  All four of the plain batch
+// variants only (no STATS, no TILES, WPG 1, TORD 0: rt_internal.h trace_variant_built).
 // The options arrive as one variant word V (rt_internal.h VF_*, vf_cls = SMAX) and are read from it by name.
 template <int K, unsigned V>
 __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
@@ -1056,6 +1146,10 @@ __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
     }
     if constexpr (SHUTTER) {
         shutter_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int rec, int tx, int ty) { return trace_tile_direct<K, V & VF_TILE>(q, tx, ty, lv, dv, tl, rec); });
+        return;
+    }
+    if constexpr ((V & VF_ADAPT) != 0) {
+        adaptive_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int pass, int tx, int ty) { return trace_tile_direct<K, V & VF_TILE>(q, tx, ty, lv, dv, tl, pass); });
         return;
     }
     const unsigned cnt = trace_tile_direct<K, V & VF_TILE>(p, tile_x, tile_y, lv, dv, tl).cnt;
@@ -1743,10 +1837,12 @@ template <int K, unsigned V, typename T>
 __device__ __forceinline__ TileOut trace_tile_bundle(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
                                                      float* stk_dv, T& tl, int rec = 0) {
     constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = (V & VF_SS) != 0, SHUTTER = (V & VF_SHUTTER) != 0;
+    constexpr bool ADAPT = (V & VF_ADAPT) != 0;
     constexpr int PATH = view_of(V);
     constexpr int MERGED = vf_cls_of(V);
     const int lane = threadIdx.x & 63;
-    const TilePixel tpx = tile_pixel<SS>(p, tile_x * TILE_W + (lane & 7), tile_y * TILE_H + (lane >> 3));
+    const TilePixel tpx = ADAPT ? sample_pixel(p, tile_x, tile_y, lane, rec)
+                                : tile_pixel<SS>(p, tile_x * TILE_W + (lane & 7), tile_y * TILE_H + (lane >> 3));
     const int x = tpx.x, y = tpx.y;
     const bool valid = tpx.valid;
 
@@ -1814,7 +1910,7 @@ __device__ __forceinline__ TileOut trace_tile_bundle(const LaunchParams& p, int 
     const f3 col = fold_converged<GPOW, MERGED, PATH>(p, stk, leaf, &cnt, tl, rec);
     const uint32_t px32 = (shift_channel(col.x) << 16) | (shift_channel(col.y) << 8) | shift_channel(col.z);
     if constexpr (TILES) encode_tile_fused(p, px32, valid);
-    else if constexpr (!SHUTTER) {
+    else if constexpr (!SHUTTER && !ADAPT) {
         // the pixel's coordinates again, from the lane id (mbcnt) and the block id: cheaper than
         // keeping x, r, y and `valid` live through the walk and the fold (64-VGPR cap: they were
         // the values spilled to scratch once the merged shadow pass raised the peak)
@@ -1863,6 +1959,10 @@ __device__ __forceinline__ void bundle_kernel_body(const LaunchParams& p) {
                            (unsigned)__builtin_amdgcn_s_memrealtime()};
     if constexpr (SHUTTER) {
         shutter_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int rec, int tx, int ty) { return trace_tile_bundle<K, V & VF_TILE>(q, tx, ty, stk_lv, stk_dv, tl, rec); });
+        return;
+    }
+    if constexpr ((V & VF_ADAPT) != 0) {
+        adaptive_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int pass, int tx, int ty) { return trace_tile_bundle<K, V & VF_TILE>(q, tx, ty, stk_lv, stk_dv, tl, pass); });
         return;
     }
     const unsigned cnt = trace_tile_bundle<K, V & VF_TILE>(p, tile_x, tile_y, stk_lv, stk_dv, tl).cnt;
@@ -1989,7 +2089,9 @@ __global__ __launch_bounds__(256) void scatter_gathered_kernel(const unsigned ch
 // lone frame on the direct kernel (wpg > 1) has wpg tiles of a tile row per workgroup, with the tile rows
 // in x when col_major is set, or a 1-D grid over the padded tile_order.
 static void trace_grid(const LaunchParams& p, const TraceVariant& v, dim3* grid, dim3* block) {
-    const unsigned tx = (unsigned)((p.W + TILE_W - 1) / TILE_W), ty = (unsigned)((p.local_rows + TILE_H - 1) / TILE_H);
+    // (ADAPT: a wave is a tile of output pixels, and W, local_rows are in samples)
+    const int as = v.mode == TM_ADAPT ? p.ss_log2 : 0;
+    const unsigned tx = (unsigned)(((p.W >> as) + TILE_W - 1) / TILE_W), ty = (unsigned)(((p.local_rows >> as) + TILE_H - 1) / TILE_H);
     const unsigned z = (unsigned)(p.n_frames > 1 ? p.n_frames : 1) + (unsigned)p.copy_z, w = (unsigned)v.wpg;
     const unsigned gxw = (tx + w - 1) / w;
     *block = dim3(WG_THREADS * w);
@@ -2037,7 +2139,7 @@ int launch_trace(const LaunchParams& p, bool generic_pow, bool stats, void* stre
     auto leaf = [&](auto consts) { return launch_built(consts, p, grid, block, (hipStream_t)stream); };
     // (pick_trace_variant returns built descriptors only: an unbuilt one is an error, not a kernel)
     if (!peel(leaf, Vals<>{}, v.family, Vals<TV_DIRECT, TV_BUNDLE>{}, v.gpow, Vals<0, 1>{}, v.mode,
-              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
+              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
               Vals<1, 2, 4, 6, 8, 64>{}, v.wpg, Vals<1, SINGLE_WPG>{}, v.tord, Vals<0, 1, 2>{}))
         return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();

@@ -51,4 +51,19 @@ RT_RESOLVE_FN uint32_t resolve_round_n(ResolveSum sum, int t) {
     return rb | (g << 8);
 }
 
+// Adaptive supersampling (rt_set_adaptive_sampling): do the pixels a and b (0x00RRGGBB) differ by at least thr,
+// thr in 1..256, in some 8-bit channel?  Per word of 16-bit fields: with bit 8 of every field of a set, a - b
+// borrows from no neighbour and the field holds 256 + (a_c - b_c) in 1..511; b - a likewise; the larger of the
+// two is 256 + |a_c - b_c|, compared field by field with 256 + thr (thr = 256: never, a difference is <= 255).
+RT_RESOLVE_FN bool adapt_field_ge(uint32_t a, uint32_t b, uint32_t lim) {  // two 16-bit fields of 8-bit values
+    const uint32_t one = 0x01000100u, d = (a | one) - b, e = (b | one) - a;
+    const uint32_t hi = (d >> 16) > (e >> 16) ? d >> 16 : e >> 16, lo = (d & 0xffffu) > (e & 0xffffu) ? d & 0xffffu : e & 0xffffu;
+    return hi >= lim || lo >= lim;
+}
+RT_RESOLVE_FN bool adapt_differs(uint32_t a, uint32_t b, int thr) {
+    const ResolveSum u = resolve_unpack(a), v = resolve_unpack(b);
+    const uint32_t lim = 256u + (uint32_t)thr;
+    return adapt_field_ge(u.rb, v.rb, lim) || adapt_field_ge(u.g, v.g, lim);
+}
+
 }  // namespace rtk

@@ -140,6 +140,18 @@ class Context:
         self._check(self.lib.rt_get_supersampling(self.ptr, C.byref(k)))
         return k.value
 
+    def set_adaptive_sampling(self, threshold: int):
+        """rt_set_adaptive_sampling: with supersampling on, only the 8x8 output tiles that hold two 4-adjacent pixels
+        differing by >= threshold (1..256) in a channel are supersampled, the others keep their one sample; 0 (the
+        default) = off, every pixel is supersampled (supersample.adaptive_resolve is the definition)."""
+        self._check(self.lib.rt_set_adaptive_sampling(self.ptr, int(threshold)))
+
+    @property
+    def adaptive_sampling(self) -> int:
+        t = C.c_int(-1)
+        self._check(self.lib.rt_get_adaptive_sampling(self.ptr, C.byref(t)))
+        return t.value
+
     def get_camera(self) -> abi.rt_camera:
         c = abi.rt_camera()
         self._check(self.lib.rt_get_camera(self.ptr, C.byref(c)))
@@ -359,13 +371,15 @@ class RayTracer:
     `debug=True` is the reference's DEBUG_ENABLE build: Tick() also composites the top-down
     ray inset (raytracer_hip.debugview) into the bottom-right corner of the frame.
     `samples` = 2, 4 or 8: every Tick() is supersampled k x k (Context.set_supersampling); the frame keeps its size.
+    `adaptive` = 1..256 with `samples` > 1: only the tiles whose pixels differ by that much are supersampled
+    (Context.set_adaptive_sampling); 0 = every pixel.
     """
 
     _KEYS = {"W": abi.RT_KEY_W, "A": abi.RT_KEY_A, "S": abi.RT_KEY_S, "D": abi.RT_KEY_D,
              "Space": abi.RT_KEY_SPACE, "LeftShift": abi.RT_KEY_SHIFT, "RightShift": abi.RT_KEY_SHIFT}
 
     def __init__(self, screen: Surface, scene: scenes.Scene | None = None, n_gpus: int = 1,
-                 debug: bool = False, debug_seed: int = 0, samples: int = 1):
+                 debug: bool = False, debug_seed: int = 0, samples: int = 1, adaptive: int = 0):
         self.screen = screen
         self.debug = debug
         self._debug_seed = debug_seed
@@ -374,6 +388,7 @@ class RayTracer:
         self._scene = sc
         self._ctx.set_scene(sc)
         self._ctx.set_supersampling(samples)
+        self._ctx.set_adaptive_sampling(adaptive)
         self._camera = sc.c_camera()
         self._ctx.register_host(screen.pixels)  # pin Surface.pixels once (D2H lands in it)
 
