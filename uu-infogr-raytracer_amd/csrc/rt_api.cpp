@@ -24,6 +24,7 @@
 
 #include "../../include/raytracer_hip.h"
 #include "rt_dark.h"
+#include "rt_foot.h"
 #include "rt_internal.h"
 
 using namespace rtk;
@@ -228,6 +229,7 @@ struct SceneLayout {
     size_t off_shg = 0, off_shgrid = 0, off_shslab = 0, off_clus = 0, off_shpre = 0;
     bool has_shpre = false;  // the direct kernel's shadow pre-test records (DevShadowCull [L][S + (S & 1)])
     bool mirror_box = true;  // the direct kernel's mirrored screen boxes (view_mirror_boxes); RT_MIRROR_BOX=0: off
+    bool prim_foot = true;   // the direct kernel's plane footprints (rt_foot.h, view_fill); RT_PRIM_FOOT=0: off
     int n_clus = 0;  // DevCluster records (the bundle kernel's per-lane pre-cull), 0: none
     bool has_shcull = false;
     bool has_shg = false;  // per-light shadow grids (DevShadowGrid) for the merged shadow pass
@@ -658,6 +660,8 @@ void copy_view(const LaunchParams& from, LaunchParams& to) {
     std::memcpy(to.mbox_plane, from.mbox_plane, sizeof to.mbox_plane);
     std::memcpy(to.mbox_tmax, from.mbox_tmax, sizeof to.mbox_tmax);
     std::memcpy(to.mbox, from.mbox, sizeof to.mbox);
+    to.foot_n = from.foot_n;
+    std::memcpy(to.foot, from.foot, sizeof to.foot);
     to.row_order_n = from.row_order_n;
     to.col_major = from.col_major;
     std::memcpy(to.row_order, from.row_order, sizeof(uint16_t) * (size_t)from.row_order_n);
@@ -687,7 +691,8 @@ int view_params(rt_ctx* ctx, int W, int H, LaunchParams& lp, int ss = 0) {
 
 // Everything of a W x VH view that depends on the camera, into the view part of lp: position and basis, the
 // view plane (pw, ph, nearc: the same for every camera of one frame size), lp.W / lp.H = the view's size, the
-// primary constants and screen boxes (prim_box) and the mirrored boxes (view_mirror_boxes).  view_params (the
+// primary constants and screen boxes (prim_box), the mirrored boxes (view_mirror_boxes) and the plane footprints
+// (rt_foot.h foot_build; a DevView record carries none: view_record).  view_params (the
 // context's camera, by value in the kernarg block) and the camera-path calls (one DevView per frame,
 // view_record) both build their views here, so a path frame carries the values a one-camera launch would.
 int view_fill(rt_ctx* ctx, const rt_camera& cam, int W, int VH, LaunchParams& lp) {
@@ -710,6 +715,12 @@ int view_fill(rt_ctx* ctx, const rt_camera& cam, int W, int VH, LaunchParams& lp
             lp.pbox[i] = prim_box(lp, sph[i]);
         }
     view_mirror_boxes(lp, ctx->layout);  // (lp.H = VH: in the view's pixels, like pbox)
+    // plane footprints (rt_foot.h): with the screen boxes they tell a wave that no primary ray of its tile hits anything
+    const std::vector<DevPlane>& pl = ctx->layout.host_pl;
+    std::memset(lp.foot, 0, sizeof lp.foot);
+    lp.foot_n = ctx->layout.prim_foot && lp.prim_const && pl.size() <= (size_t)FOOT_MAX
+                    ? foot_build(lp, pl.data(), (int)pl.size(), lp.foot)
+                    : -1;
     return RT_OK;
 }
 
@@ -1791,6 +1802,9 @@ int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_
     // the dark-tile skip (rt_dark.h): planes whose material and the scene's lights pass the host part of its guard;
     // RT_DARK_SKIP=0 leaves the bit clear (A/B)
     const char* dv = std::getenv("RT_DARK_SKIP");
+    // the plane footprints of a view (rt_foot.h, built per view by view_fill); RT_PRIM_FOOT=0 turns them off (A/B)
+    const char* fv = std::getenv("RT_PRIM_FOOT");
+    L.prim_foot = !(fv && std::strcmp(fv, "0") == 0);
     if (!(dv && std::strcmp(dv, "0") == 0))
         for (int i = 0; i < n_planes; ++i)
             if (plane_dark_ok(pl[i], mat[n_spheres + i], li, n_lights)) mat[n_spheres + i].flags |= MAT_DARK_OK;

@@ -146,6 +146,11 @@ struct PrimConst {
     float ocx, ocy, ocz, c;
 };
 constexpr int MAX_PRIM_CONST = 64;
+// Per-view footprint of a plane for primary rays (rt_foot.h derives it and states the rule).
+struct PlaneFoot {
+    float a, b, c;
+};
+constexpr int FOOT_MAX = 4;
 constexpr int ROW_ORDER_MAX = 272;  // tile rows of a 2176-row frame (4K UHD: 270)
 
 // Scenes with at least this many spheres use wave-bundle culling (rt_kernel.hip; the bundle
@@ -268,6 +273,13 @@ struct LaunchParams {
     // two 4-adjacent pixels of the tile differ by >= T in a channel (rt_kernel.hip adaptive_tile); the grid is in
     // output tiles.  Last: no other field moves.
     int adapt_thr;
+    // Plane footprints of the view (rt_foot.h; the direct kernel's one-view instantiations; culling only): foot_n
+    // >= 0: the scene has foot_n = P planes and foot[i] is plane i's record -- a pixel with view-table values
+    // (lx, ly) cannot select plane i with its primary ray when fma(a, lx, fma(b, ly, c)) < 0.  -1: none (the view
+    // or a plane outside the rule's domain, more than FOOT_MAX planes, no primary constants, RT_PRIM_FOOT=0).
+    // Last: no other field moves.
+    int foot_n;
+    PlaneFoot foot[FOOT_MAX];
 };
 constexpr int MIRROR_BOX_PLANES = 2;
 // Tiles per workgroup of the direct kernel's single-frame launches (8: +2.5 % on C2,

@@ -26,6 +26,7 @@
 #include "rt_fastmath.h"
 #include "rt_codec_common.h"
 #include "rt_dark.h"
+#include "rt_foot.h"
 #include "rt_internal.h"
 #include "rt_pow.h"
 #include "rt_prims.h"
@@ -253,6 +254,12 @@ struct ViewOf {
     __device__ __forceinline__ const PrimBox* mbox(int k) const {
         if constexpr (PATH != VIEW_ARGS) return v().mbox[k];
         else return p.mbox[k];
+    }
+    // plane footprints (rt_foot.h): the one-view launches only -- a DevView record carries none, so the PATH and
+    // SHUTTER instantiations compile nothing of the sky test
+    __device__ __forceinline__ int foot_n() const {
+        if constexpr (PATH != VIEW_ARGS) return -1;
+        else return p.foot_n;
     }
 };
 
@@ -857,6 +864,24 @@ __device__ __forceinline__ Hit terminal_direct(const LaunchParams& p, f3 o, f3 d
     return Hit{best_p, ~win_p};
 }
 
+// Sky waves (rt_foot.h): no primary ray of the wave's pixels can select a sphere -- its pixels lie
+// outside every screen box, pmask == 0 with the primary constants on -- or a plane: every valid lane fails every
+// plane's footprint rule.  Such a wave's pixels are 0 and it casts no reflected or shadow ray.  Converged call;
+// false without footprints (foot_n < 0: always in the PATH and SHUTTER instantiations, which compile none of this).
+template <int PATH>
+__device__ __forceinline__ bool sky_tile(const LaunchParams& p, const TilePixel& t, unsigned long long pmask, int rec) {
+    const ViewOf<PATH> vw{p, rec};
+    const int n = vw.foot_n();
+    if (n < 0 || pmask != 0 || !vw.prim_const()) return false;  // wave-uniform
+    bool may = false;
+#pragma unroll
+    for (int i = 0; i < FOOT_MAX; ++i) {
+        if (i >= n) break;  // wave-uniform
+        may |= foot_may_hit(p.foot[i], t.lx, t.ly);
+    }
+    return __builtin_amdgcn_ballot_w64(t.valid && may) == 0;
+}
+
 // What of a variant word (rt_internal.h VF_*) the trace of one tile depends on: everything but the workgroup
 // shape and the tile order, which only pick the tile.  The kernel bodies hand trace_tile_{direct,bundle} the word
 // masked by it, so one instantiation serves every shape and order.
@@ -886,70 +911,76 @@ __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int 
     const bool valid = tpx.valid;
     const ViewOf<PATH> vw{p, rec};
     const unsigned long long pmask = vw.prim_const() ? prim_box_mask<PATH>(p, x, y, rec) : 0;
+    // a sky wave traces nothing: every valid lane's pixel is 0, no ray beyond the primary ones, no tally
+    const bool sky = sky_tile<PATH>(p, tpx, pmask, rec);  // wave-uniform
     // K == 1 (limit 0): level 1 is a terminal segment, nothing of the mirrored boxes is compiled in
     unsigned mmask = 0;
-    if constexpr (K > 1) mmask = mirror_box_masks<PATH>(p, x, y, rec);
+    if constexpr (K > 1) {
+        if (!sky) mmask = mirror_box_masks<PATH>(p, x, y, rec);
+    }
 
     unsigned cnt = 0;  // packed: reflected segments (bits 0-7) | shadow rays << CNT_SHADOW_SHIFT
     typename StackFor<K>::type stk(stk_lv, stk_dv);
     f3 leaf = mk(0.0f, 0.0f, 0.0f);
     uint32_t px32 = 0;
     if (valid) {
-        const f3 cam = vw.cam();
-        // TracePixel primary ray, :963-971 (no half-pixel offset)
-        // lx = ((float)x / W - 0.5f) * pw, ly likewise: per-column / per-row tables built on
-        // the host with the same binary32 operations (view_tables in rt_api.cpp)
-        const float lx = tpx.lx, ly = tpx.ly, lz = 1.0f * p.nearc;
-        const f3 vp = add(add(add(cam, scale(vw.right(), lx)), scale(vw.up(), ly)), scale(vw.fwd(), lz));
-        f3 d = normalize(sub(vp, cam));
-        f3 o = cam;
+        if (!sky) {  // wave-uniform
+            const f3 cam = vw.cam();
+            // TracePixel primary ray, :963-971 (no half-pixel offset)
+            // lx = ((float)x / W - 0.5f) * pw, ly likewise: per-column / per-row tables built on
+            // the host with the same binary32 operations (view_tables in rt_api.cpp)
+            const float lx = tpx.lx, ly = tpx.ly, lz = 1.0f * p.nearc;
+            const f3 vp = add(add(add(cam, scale(vw.right(), lx)), scale(vw.up(), ly)), scale(vw.fwd(), lz));
+            f3 d = normalize(sub(vp, cam));
+            f3 o = cam;
 
-        stk.origin(d);
-        Hit h = nearest_direct<true, false, PATH>(p, o, d, tl, pmask, rec);
-        int count = 0;
-        for (;;) {
-            if (h.prim == HIT_NONE) break;      // nothing hit: plane colour stays Zero
-            if (h.t - 0.01f <= 0.0f) break;     // too close: Zero (:731, :839)
-            const bool is_sphere = h.prim >= 0;
-            if (count > p.limit) {              // terminal segment: Zero / One (:734, :843)
-                if (!is_sphere) leaf = mk(1.0f, 1.0f, 1.0f);
-                break;
+            stk.origin(d);
+            Hit h = nearest_direct<true, false, PATH>(p, o, d, tl, pmask, rec);
+            int count = 0;
+            for (;;) {
+                if (h.prim == HIT_NONE) break;      // nothing hit: plane colour stays Zero
+                if (h.t - 0.01f <= 0.0f) break;     // too close: Zero (:731, :839)
+                const bool is_sphere = h.prim >= 0;
+                if (count > p.limit) {              // terminal segment: Zero / One (:734, :843)
+                    if (!is_sphere) leaf = mk(1.0f, 1.0f, 1.0f);
+                    break;
+                }
+                // shaded hit: record it; mirror hits continue with the reflected segment
+                const f3 hp = add(o, scale(d, h.t));
+                stk.push(make_float4(hp.x, hp.y, hp.z, h.t), make_float4(d.x, d.y, d.z, __int_as_float(h.prim)));
+                const int prim = is_sphere ? h.prim : ~h.prim;
+                const uint32_t flags = p.mat[is_sphere ? prim : p.S + prim].flags;
+                if (!(flags & MAT_MIRROR)) break;
+                o = reflect_at(p, o, d, h.t, h.prim);  // :854, CalculateReflectionRay :718-720
+                ++count;
+                ++cnt;
+                // count is the same for every lane still walking: no divergence here
+                if constexpr (K > 1) {
+                    // the first reflected segment: the spheres its mirrored boxes allow (when the wave has tables)
+                    // (count read from the first active lane: a scalar branch, and the mask stays wave-uniform)
+                    unsigned smask = ~0u;
+                    if (vw.mbox_n() > 0 && __builtin_amdgcn_readfirstlane(count) == 1) smask = mirror_box_select<PATH>(p, mmask, h.t, h.prim, rec);
+                    h = count > p.limit ? terminal_direct(p, o, d, tl) : nearest_direct<false, true>(p, o, d, tl, smask);
+                } else {
+                    h = count > p.limit ? terminal_direct(p, o, d, tl) : nearest_direct<false>(p, o, d, tl);
+                }
             }
-            // shaded hit: record it; mirror hits continue with the reflected segment
-            const f3 hp = add(o, scale(d, h.t));
-            stk.push(make_float4(hp.x, hp.y, hp.z, h.t), make_float4(d.x, d.y, d.z, __int_as_float(h.prim)));
-            const int prim = is_sphere ? h.prim : ~h.prim;
-            const uint32_t flags = p.mat[is_sphere ? prim : p.S + prim].flags;
-            if (!(flags & MAT_MIRROR)) break;
-            o = reflect_at(p, o, d, h.t, h.prim);  // :854, CalculateReflectionRay :718-720
-            ++count;
-            ++cnt;
-            // count is the same for every lane still walking: no divergence here
-            if constexpr (K > 1) {
-                // the first reflected segment: the spheres its mirrored boxes allow (when the wave has tables)
-                // (count read from the first active lane: a scalar branch, and the mask stays wave-uniform)
-                unsigned smask = ~0u;
-                if (vw.mbox_n() > 0 && __builtin_amdgcn_readfirstlane(count) == 1) smask = mirror_box_select<PATH>(p, mmask, h.t, h.prim, rec);
-                h = count > p.limit ? terminal_direct(p, o, d, tl) : nearest_direct<false, true>(p, o, d, tl, smask);
-            } else {
-                h = count > p.limit ? terminal_direct(p, o, d, tl) : nearest_direct<false>(p, o, d, tl);
+            // backward fold: every recorded hit is shaded in reverse order; a mirror hit
+            // consumes the colour of the segment after it (levels 0..limit push at most one
+            // record each, so K = limit + 1 records suffice).  Per lane, divergent: the bundle
+            // kernel's converged fold with wave-level shadow culling measured slower here (C2
+            // +14 %, C3 +17 %, profiles/ab/r02_direct_converged_fold_rejected.txt)
+            f3 col = leaf;
+            while (stk.n > 0) {
+                float4 ra, rb;
+                stk.template pop<PATH>(p, ra, rb, rec);
+                const int code = __float_as_int(rb.w);
+                const bool is_s = code >= 0;
+                col = shade_direct<GPOW>(p, is_s, is_s ? code : ~code, mk(ra.x, ra.y, ra.z),
+                                               mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl);
             }
+            px32 = (shift_channel(col.x) << 16) | (shift_channel(col.y) << 8) | shift_channel(col.z);
         }
-        // backward fold: every recorded hit is shaded in reverse order; a mirror hit
-        // consumes the colour of the segment after it (levels 0..limit push at most one
-        // record each, so K = limit + 1 records suffice).  Per lane, divergent: the bundle
-        // kernel's converged fold with wave-level shadow culling measured slower here (C2
-        // +14 %, C3 +17 %, profiles/ab/r02_direct_converged_fold_rejected.txt)
-        f3 col = leaf;
-        while (stk.n > 0) {
-            float4 ra, rb;
-            stk.template pop<PATH>(p, ra, rb, rec);
-            const int code = __float_as_int(rb.w);
-            const bool is_s = code >= 0;
-            col = shade_direct<GPOW>(p, is_s, is_s ? code : ~code, mk(ra.x, ra.y, ra.z),
-                                           mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl);
-        }
-        px32 = (shift_channel(col.x) << 16) | (shift_channel(col.y) << 8) | shift_channel(col.z);
         if constexpr (!TILES && !SS && !SHUTTER && !ADAPT) store_pixel(p, r, y, x, px32);
     }
     if constexpr (TILES) encode_tile_fused(p, px32, valid);
