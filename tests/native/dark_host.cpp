@@ -1,5 +1,5 @@
 // Host check of the dark-tile skip's guard (csrc/rt_dark.h; tests/test_dark_host.py), TEST INFRASTRUCTURE ONLY.
-// Built by dark.mk as host C++ with ASan + UBSan and -ffp-contract=off, run as a plain executable on the CPU.
+// Built by the Makefile beside it as host C++ with ASan + UBSan and -ffp-contract=off, run as a plain executable on the CPU.
 //
 // The per-light term of a plane hit (RayTracer.cs ShapePhongShading :665-695 and TracePlane's addend :752-775) is
 // restated here in binary32 and evaluated over a product of edge inputs.
@@ -73,7 +73,7 @@ V3 addend(float inten, V3 hp, V3 d, float t, V3 normal, const Mat& m, V3 lp, flo
 }
 bool plus_zero(V3 v) { return bits(v.x) == 0 && bits(v.y) == 0 && bits(v.z) == 0; }
 
-// the device records as rt_set_scene builds them (rt_api.cpp dev_material, DevPlane, DevLight)
+// the device records as rt_set_scene builds them (rt_scene.h dev_material, DevPlane, DevLight)
 DevMaterial dev_mat(const Mat& m) {
     DevMaterial d;
     std::memset(&d, 0, sizeof d);

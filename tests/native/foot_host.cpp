@@ -1,5 +1,6 @@
 // Host check of the plane footprints (csrc/rt_foot.h; tests/test_foot_host.py), TEST INFRASTRUCTURE ONLY.
-// Built by foot.mk as host C++ with ASan + UBSan and -ffp-contract=off, run as a plain executable on the CPU.
+// Built by the Makefile beside it (its pure rule) as host C++ with ASan + UBSan and -ffp-contract=off, run as a plain
+// executable on the CPU.  The views, screen boxes and view-table values are the library's own (csrc/rt_view.h).
 //
 // The kernel's primary direction (trace_tile_direct: the view-plane point, vp - cam, Vector3.Normalize) and
 // plane_take's `may` are restated here in binary32, in the kernel's operation order, and evaluated at every pixel of
@@ -7,16 +8,17 @@
 //   1. Soundness: wherever a footprint's rule says "cannot hit", may is false.  Zero failures.
 //   2. Teeth: the same sweep with the footprints built without margins (foot_build(..., margins = false)) has
 //      failures -- the cameras far from the origin are there for that.
-//   3. Effect: on C3's 1920 x 1080 view the rule and the spheres' screen boxes (prim_box, restated below) leave at
+//   3. Effect: on C3's 1920 x 1080 view the rule and the spheres' screen boxes (rt_view.h prim_box) leave at
 //      least 12,500 of the 32,400 tiles with nothing to trace, and none on a view that looks straight down.
 #include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "rt_foot.h"
+#include "rt_view.h"
 
 using namespace rtk;
 
@@ -29,32 +31,17 @@ V3 sub(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
 V3 add(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
 V3 scale(V3 a, float s) { return V3{a.x * s, a.y * s, a.z * s}; }
 float dot(V3 a, V3 b) { return ((a.x * b.x) + (a.y * b.y)) + (a.z * b.z); }  // Vector3.Dot
-V3 cross(V3 l, V3 r) { return V3{(l.y * r.z) - (l.z * r.y), (l.z * r.x) - (l.x * r.z), (l.x * r.y) - (l.y * r.x)}; }
 V3 normalize(V3 a) {  // Vector3.Normalize
     const float s = 1.0f / std::sqrt(dot(a, a));
     return scale(a, s);
 }
 
-// rt_camera_view: the basis and the view plane of a camera
+// The library's view of a camera on a W x H frame (rt_view.h view_build; no scene: the sweep brings its own planes)
 void view_of(V3 pos, double yaw, double pitch, int W, int H, LaunchParams& lp) {
     std::memset(&lp, 0, sizeof lp);
-    const V3 f{(float)(std::cos(pitch) * std::sin(yaw)), (float)-std::sin(pitch), (float)(std::cos(pitch) * std::cos(yaw))};
-    const V3 r{(float)std::cos(yaw), 0.0f, (float)-std::sin(yaw)};
-    const V3 u = cross(r, f);
-    lp.cam[0] = pos.x, lp.cam[1] = pos.y, lp.cam[2] = pos.z;
-    lp.right[0] = r.x, lp.right[1] = r.y, lp.right[2] = r.z;
-    lp.up[0] = u.x, lp.up[1] = u.y, lp.up[2] = u.z;
-    lp.fwd[0] = f.x, lp.fwd[1] = f.y, lp.fwd[2] = f.z;
-    const float near_clip = 0.3f, fov = 60.0f;
-    const float deg2rad = (float)M_PI / 180.0f;
-    const float rad = (fov * 0.5f) * deg2rad;
-    const float plane_height = near_clip * (float)std::tan((double)rad) * 2;
-    lp.pw = plane_height * ((float)W / (float)H), lp.ph = plane_height, lp.nearc = near_clip;
-    lp.W = W, lp.H = H;
-    lp.prim_const = 1;
+    const rt_camera cam{rt_vec3{pos.x, pos.y, pos.z}, (float)yaw, (float)pitch};
+    if (view_build(SceneLayout{}, cam, W, H, lp) != RT_OK) std::abort();
 }
-// view_tables: lxt[x] = ((float)x / W - 0.5f) * pw
-float table(int i, int n, float plane) { return ((float)i / (float)n - 0.5f) * plane; }
 
 // trace_tile_direct's primary direction
 V3 primary_dir(const LaunchParams& lp, float lx, float ly) {
@@ -97,39 +84,6 @@ V3 unit() {
     }
 }
 
-// prim_box of rt_api.cpp, restated (extra = 0): the conservative screen box of a sphere for primary rays
-PrimBox prim_box(const LaunchParams& lp, const DevSphere& s) {
-    const PrimBox all{INT_MIN / 2, INT_MAX / 2, INT_MIN / 2, INT_MAX / 2};
-    const double pw = lp.pw, ph = lp.ph, lz = lp.nearc;
-    const double cam[3] = {lp.cam[0], lp.cam[1], lp.cam[2]};
-    const double u[3] = {s.cx - cam[0], s.cy - cam[1], s.cz - cam[2]};
-    auto dot3 = [](const double* a, const float* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
-    const double ulen = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    const double camlen = std::sqrt(cam[0] * cam[0] + cam[1] * cam[1] + cam[2] * cam[2]);
-    const double dmax = std::sqrt(0.25 * pw * pw + 0.25 * ph * ph + lz * lz);
-    const double dir_err = 0x1p-20 * (camlen + dmax) / lz + 0x1p-20;
-    const double r = std::sqrt((double)s.r2);
-    if (!(dir_err <= 0x1p-12)) return all;
-    const double rho = (r * (1.0 + 0x1p-8) + (0x1p-8 + 0x1p-20 + dir_err) * ulen) * (1.0 + 0x1p-16) + 0x1p-60;
-    const double cx = dot3(u, lp.right), cy = dot3(u, lp.up), cz = dot3(u, lp.fwd);
-    if (!(cz > rho * (1.0 + 0x1p-10))) return all;
-    auto range = [&](double c, double pl, int n, int& lo, int& hi) {
-        const double phi = std::atan2(c, cz);
-        const double g = std::asin(std::min(1.0, rho / std::sqrt(c * c + cz * cz)));
-        const double flo = n * (0.5 + lz * std::tan(phi - g) / pl), fhi = n * (0.5 + lz * std::tan(phi + g) / pl);
-        if (!std::isfinite(flo) || !std::isfinite(fhi)) {
-            lo = INT_MIN / 2, hi = INT_MAX / 2;
-            return;
-        }
-        lo = (int)std::max(-1e9, std::floor(flo) - 2.0);
-        hi = (int)std::min(1e9, std::ceil(fhi) + 2.0);
-    };
-    PrimBox b;
-    range(cx, pw, lp.W, b.x0, b.x1);
-    range(cy, ph, lp.H, b.y0, b.y1);
-    return b;
-}
-
 // raytracer_hip/scenes.py generated_spheres(8): the C2 / C3 spheres (centres and radii)
 std::vector<DevSphere> c3_spheres() {
     std::vector<DevSphere> s{{2.5f, 0, 8, 1.0f}, {3, 0, 5, 1.0f}, {-3, 1, 8, 1.0f}};
@@ -163,6 +117,8 @@ int sky_tiles(const LaunchParams& lp, const std::vector<DevSphere>& sph, const s
     if (n < 0) return 0;
     std::vector<PrimBox> box;
     for (const DevSphere& s : sph) box.push_back(prim_box(lp, s));
+    std::vector<float> tab((size_t)lp.W + (size_t)lp.H);  // lx[W] then ly[H]
+    view_table_values(lp.W, lp.H, lp.pw, lp.ph, tab.data());
     int count = 0;
     for (int ty = 0; ty < (lp.H + 7) / 8; ++ty)
         for (int tx = 0; tx < (lp.W + 7) / 8; ++tx) {
@@ -171,7 +127,7 @@ int sky_tiles(const LaunchParams& lp, const std::vector<DevSphere>& sph, const s
             for (const PrimBox& b : box) cand |= b.x0 <= x_hi && b.x1 >= x_lo && b.y0 <= y_hi && b.y1 >= y_lo;
             for (int y = y_lo; y <= y_hi && y < lp.H && !cand; ++y)
                 for (int x = x_lo; x <= x_hi && x < lp.W && !cand; ++x)
-                    for (int i = 0; i < n; ++i) cand |= foot_may_hit(foot[i], table(x, lp.W, lp.pw), table(y, lp.H, lp.ph));
+                    for (int i = 0; i < n; ++i) cand |= foot_may_hit(foot[i], tab[(size_t)x], tab[(size_t)lp.W + (size_t)y]);
             count += !cand;
         }
     return count;
@@ -207,7 +163,7 @@ int main() {
 
     long long views = 0, checked = 0, excluded = 0, failures = 0, off = 0, teeth_excluded = 0, teeth_failures = 0;
     std::vector<V3> dir;
-    std::vector<float> lxs, lys;
+    std::vector<float> tab;  // the view tables: lx[W] then ly[H]
     for (const V3& cam : cams)
         for (double pitch : pitches)
             for (double yaw : yaws) {
@@ -216,9 +172,9 @@ int main() {
                 LaunchParams lp;
                 view_of(cam, yaw, pitch, sz[0], sz[1], lp);
                 const int W = sz[0], H = sz[1];
-                dir.resize((size_t)W * H), lxs.resize((size_t)W), lys.resize((size_t)H);
-                for (int x = 0; x < W; ++x) lxs[(size_t)x] = table(x, W, lp.pw);
-                for (int y = 0; y < H; ++y) lys[(size_t)y] = table(y, H, lp.ph);
+                dir.resize((size_t)W * H), tab.resize((size_t)W + (size_t)H);
+                view_table_values(W, H, lp.pw, lp.ph, tab.data());
+                const float *lxs = tab.data(), *lys = tab.data() + W;
                 for (int y = 0; y < H; ++y)
                     for (int x = 0; x < W; ++x) dir[(size_t)y * W + x] = primary_dir(lp, lxs[(size_t)x], lys[(size_t)y]);
                 auto sweep = [&](const DevPlane& q, const PlaneFoot& f, long long& n_excl, long long& n_fail) {

@@ -1,6 +1,6 @@
-// mirror_box_host.cpp -- host check of the direct kernel's mirrored screen boxes (rt_api.cpp mirror_boxes /
-// view_mirror_boxes, LaunchParams::mbox), TEST INFRASTRUCTURE ONLY.  rt_api.cpp is compiled into this translation
-// unit (unity include, as in san_host.cpp) under host-side ASan + UBSan; no device call is reached.
+// mirror_box_host.cpp -- host check of the direct kernel's mirrored screen boxes (csrc/rt_view.h mirror_boxes /
+// view_mirror_boxes, LaunchParams::mbox), TEST INFRASTRUCTURE ONLY.  Plain host C++ against the library's device-free
+// builders (rt_scene.h scene_build, rt_view.h view_build) under ASan + UBSan; no device code is compiled or linked.
 //
 // Random scenes of 1-11 spheres over the scales of san_host.cpp's check_shadow_pre (1e-3, 1, 30, 1000) with 1-3
 // mirror planes -- floors, tilted planes, planes just under or over the camera, the camera on either side,
@@ -17,12 +17,17 @@
 //
 // Prints "mirror_box: <n> (pixel, plane, sphere) triples outside a box, <f> failures" and
 // "mirror_box_nomargin: <m> triples, <g> failures"; exit status 0 iff f == 0 and g > 0.
-#include "../../uu-infogr-raytracer_amd/csrc/rt_api.cpp"
-
+#include <climits>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "rt_view.h"
 
 #include "../../oracle/oracle.h"
+
+using namespace rtk;
 
 namespace {
 uint64_t rng = 0xB0C5ED5EEDull;
@@ -171,18 +176,12 @@ void run(Counts& with, Counts& without) {
             pl[0].center.y = cam.position.y - unif(0.5f, 2.0f) * ts;
         }
         rt_light li{v3(0, 10, 0), 1.0f};
-        rt_ctx ctx;
-        if (rt_set_scene(&ctx, sph.data(), S, pl.data(), P, &li, 1, v3(0.1f, 0.1f, 0.1f), 3) != RT_OK) {
-            std::fprintf(stderr, "FAIL scene %d: rt_set_scene\n", it);
-            ++with.failures;
-            continue;
-        }
-        rt_set_camera(&ctx, &cam);
+        const SceneLayout layout = scene_build(sph.data(), S, pl.data(), P, &li, 1, v3(0.1f, 0.1f, 0.1f), 3);
         const int W = it % 3 == 0 ? 1920 : it % 3 == 1 ? 4001 : 333, H = it % 3 == 0 ? 1080 : it % 3 == 1 ? 3001 : 250;
         LaunchParams lp;
         std::memset(&lp, 0, sizeof lp);
-        if (view_params(&ctx, W, H, lp) != RT_OK) {
-            std::fprintf(stderr, "FAIL scene %d: view_params\n", it);
+        if (view_build(layout, cam, W, H, lp) != RT_OK) {
+            std::fprintf(stderr, "FAIL scene %d: view_build\n", it);
             ++with.failures;
             continue;
         }
@@ -208,7 +207,7 @@ void run(Counts& with, Counts& without) {
             // teeth: the same plane's boxes without the allowances
             PrimBox bare[CULL_MIN_SPHERES];
             float tm = 0.0f;
-            if (mirror_boxes(lp, ctx.layout.host_pl[(size_t)j], ctx.layout.host_sph, bare, &tm, false))
+            if (mirror_boxes(lp, layout.host_pl[(size_t)j], layout.host_sph, bare, &tm, false))
                 check_table(lp, W, H, pl[(size_t)j], bare, tm, sph, without, false, it);
         }
         no_tables += std::min(P, MIRROR_BOX_PLANES) - lp.mbox_n;

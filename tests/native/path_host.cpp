@@ -1,4 +1,4 @@
-// path_host.cpp -- host check of the camera-path view records (rt_api.cpp view_fill / view_record, DevView in
+// path_host.cpp -- host check of the camera-path view records (rt_api.cpp view_fill over rt_view.h view_build / view_record, DevView in
 // rt_internal.h), TEST INFRASTRUCTURE ONLY.  rt_api.cpp is compiled into this translation unit (its helpers have
 // internal linkage) with host-side ASan + UBSan; no device call is reached (contexts without devices).
 //

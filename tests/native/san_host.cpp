@@ -11,7 +11,7 @@
 //     and degenerate cameras, cross-checked bit for bit against the oracle's camera view;
 //   * OnKeyPress / OnMouseMove (:543-554, :1058-1061), rt_write_ppm, rt_wire_layout_of,
 //     and the argument checks of every entry point (no device call is reached);
-//   * the Tick hand-off's band plan and copy jobs (for_band_copies, share_job): every frame word once.
+//   * the Tick hand-off's band plan and copy jobs (rt_bands.h for_band_copies, share_job): every frame word once.
 // Exit status 0 = all checks passed; any sanitizer report aborts the process.
 #include "../../uu-infogr-raytracer_amd/csrc/rt_api.cpp"
 
@@ -248,7 +248,7 @@ void check_shadow_threshold() {
     std::printf("shadow_threshold: %ld (n, 2a) pairs\n", checked);
 }
 
-// The per-light shadow grids (rt_set_scene -> build_shadow_grid; looked up by rt_kernel.hip
+// The per-light shadow grids (rt_set_scene -> rt_scene.h build_shadow_grid; looked up by rt_kernel.hip
 // shadow_members_grid): for random scenes -- unit, large and huge coordinates, tiny / zero / NaN
 // radii, grazing and degenerate lights -- and hit points near sphere surfaces, on grazing shadow
 // lines, on cell and slab edges, far beyond the table's bound and non-finite, a sphere the lookup

@@ -1,5 +1,5 @@
 // variant_host.cpp -- host check of the trace kernels' variant selection (rt_internal.h pick_trace_variant), TEST
-// INFRASTRUCTURE ONLY.  Built by variant.mk under ASan + UBSan and run as a plain executable on the CPU
+// INFRASTRUCTURE ONLY.  Built by the Makefile beside it under ASan + UBSan and run as a plain executable on the CPU
 // (tests/test_variant_host.py); needs rt_internal.h alone, no device call exists here.
 //
 // Every combination of the launch parameters the selection reads is enumerated, and each result compared with

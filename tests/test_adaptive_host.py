@@ -1,31 +1,18 @@
 """Host checks of adaptive supersampling (rt_set_adaptive_sampling): CPU only.
-tests/native/adaptive_host.cpp, built by tests/native/adaptive.mk under host-side ASan + UBSan and run as a plain
+tests/native/adaptive_host.cpp, built by tests/native/Makefile under host-side ASan + UBSan and run as a plain
 executable, checks the kernels' difference / threshold function against plain integer code, the argument checks of
 both calls, the band-row rule on a context without devices, and the variant selection with a threshold (504
 descriptors, 444 of them without one and selected as before)."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-EXE = os.path.join(NATIVE, "build", "adaptive_host")
+import host_check
 
 
 @pytest.fixture(scope="module")
 def output():
-    subprocess.run(["make", "-s", "-f", "adaptive.mk", "-C", NATIVE], check=True, timeout=1800)
-    env = dict(os.environ)
-    # a preloaded library (if any) stays: ASan is told not to insist on coming first
-    env["ASAN_OPTIONS"] = ":".join(x for x in (env.get("ASAN_OPTIONS", ""), "verify_asan_link_order=0") if x)
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1"
-    r = subprocess.run([EXE], capture_output=True, text=True, timeout=600, env=env)
-    out = r.stdout + r.stderr
-    for marker in ("ERROR: AddressSanitizer", "runtime error:", "ERROR: LeakSanitizer"):
-        assert marker not in out, out[-4000:]
-    assert r.returncode == 0, out[-4000:]
+    out = host_check.run("adaptive_host", run_timeout=600)
     assert "adaptive_host: 0 failures" in out, out[-4000:]
     return out
 

@@ -1,35 +1,21 @@
 """Host check of the plane footprints (csrc/rt_foot.h): CPU only.  tests/native/foot_host.cpp, built by
-tests/native/foot.mk under host-side ASan + UBSan without FMA contraction and run as a plain executable, restates the
-kernel's primary direction and plane_take's `may` in binary32 and evaluates them at every pixel of 64 x 40, 37 x 23
+tests/native/Makefile under host-side ASan + UBSan without FMA contraction and run as a plain executable, takes its
+views, screen boxes and view tables from the library's csrc/rt_view.h, restates the kernel's primary direction and plane_take's `may` in binary32 and evaluates them at every pixel of 64 x 40, 37 x 23
 and 100 x 60 frames for 11 cameras (at the origin, below and exactly on the floor, up to 1e4 away) x 14 pitches x 7
 yaws, against plane sets of 0 to 5 planes: the floor, arbitrary normals, normals scaled by 1e-3 and 1e3, |cn| up to
 1e6, zero, NaN and inf normals.  Wherever a footprint says "cannot hit", may is false; the same sweep with
 footprints built without margins does report failures; and on C3's 1920 x 1080 view the rule and the spheres' screen
 boxes leave at least 12,500 of the 32,400 tiles with nothing to trace, none on a view that looks straight down."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-EXE = os.path.join(NATIVE, "build", "foot_host")
+import host_check
 
 
 @pytest.fixture(scope="module")
 def output():
-    subprocess.run(["make", "-s", "-f", "foot.mk", "-C", NATIVE], check=True, timeout=600)
-    env = dict(os.environ)
-    # a preloaded library (if any) stays: ASan is told not to insist on coming first
-    env["ASAN_OPTIONS"] = ":".join(x for x in (env.get("ASAN_OPTIONS", ""), "verify_asan_link_order=0") if x)
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1"
-    r = subprocess.run([EXE], capture_output=True, text=True, timeout=300, env=env)
-    out = r.stdout + r.stderr
-    for marker in ("ERROR: AddressSanitizer", "runtime error:", "ERROR: LeakSanitizer"):
-        assert marker not in out, out[-4000:]
-    assert r.returncode == 0, out[-4000:]
-    return out
+    return host_check.run("foot_host")
 
 
 def test_no_plane_is_selectable_where_its_footprint_excludes_it(output):

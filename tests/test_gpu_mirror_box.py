@@ -1,5 +1,5 @@
 """Mirrored screen boxes of the direct kernel (S < 12 spheres, limit >= 1): the first reflected segment off a boxed
-mirror plane tests only the spheres whose mirrored box (rt_api.cpp mirror_boxes, LaunchParams::mbox) meets the
+mirror plane tests only the spheres whose mirrored box (rt_view.h mirror_boxes, LaunchParams::mbox) meets the
 wave's pixels.  Culling only: with the boxes on (the default) and off (RT_MIRROR_BOX=0, read by rt_set_scene) every
 frame and every ray count equals the oracle's.  Frames of at most 160 x 96; each oracle frame is rendered once per
 module and shared read-only.

@@ -135,7 +135,7 @@ def shadow_grid_scene(seed, width=160, height=96):
 @pytest.mark.parametrize("seed", list(range(30)))
 def test_shadow_grid_scenes_vs_oracle(gpu_ctx, oracle, seed, monkeypatch):
     """The bundle kernel's merged shadow pass takes each lane's sphere candidates from per-light
-    grids (rt_api.cpp build_shadow_grid); RT_SHADOW_GRID=0 at rt_set_scene keeps the per-level
+    grids (rt_scene.h build_shadow_grid); RT_SHADOW_GRID=0 at rt_set_scene keeps the per-level
     bound instead.  Both must give the oracle's pixels and ray counts."""
     sc = shadow_grid_scene(seed)
     want, ost = oracle.render(sc, oracle.MODE_NEAREST, 8)

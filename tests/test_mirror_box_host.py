@@ -1,34 +1,20 @@
-"""Host check of the direct kernel's mirrored screen boxes (rt_api.cpp mirror_boxes): CPU only.
-tests/native/mirror_box_host.cpp, built by tests/native/mirror_box.mk under host-side ASan + UBSan and run as a
-plain executable, draws random scenes (1-11 spheres, 1-3 mirror planes: tilted, next to the camera, the camera on
+"""Host check of the direct kernel's mirrored screen boxes (csrc/rt_view.h mirror_boxes): CPU only.
+tests/native/mirror_box_host.cpp, built by tests/native/Makefile as plain host C++ on csrc/rt_scene.h and rt_view.h under ASan + UBSan and run as
+a plain executable, draws random scenes (1-11 spheres, 1-3 mirror planes: tilted, next to the camera, the camera on
 either side, normals off unit length, spheres touching / cutting / behind the plane, cameras far from the origin)
 and, for every sampled pixel outside a sphere's mirrored box whose primary ray meets the plane within t_max, runs
 the oracle's binary32 chain -- primary ray, IntersectPlane, reflection, IntersectsSphere -- which must report no
 collision.  The same boxes without the added allowances must fail that check (the allowances are needed)."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-EXE = os.path.join(NATIVE, "build", "mirror_box_host")
+import host_check
 
 
 @pytest.fixture(scope="module")
 def output():
-    subprocess.run(["make", "-s", "-f", "mirror_box.mk", "-C", NATIVE], check=True, timeout=900)
-    env = dict(os.environ)
-    # a preloaded library (if any) stays: ASan is told not to insist on coming first
-    env["ASAN_OPTIONS"] = ":".join(x for x in (env.get("ASAN_OPTIONS", ""), "verify_asan_link_order=0") if x)
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1"
-    r = subprocess.run([EXE], capture_output=True, text=True, timeout=300, env=env)
-    out = r.stdout + r.stderr
-    for marker in ("ERROR: AddressSanitizer", "runtime error:", "ERROR: LeakSanitizer"):
-        assert marker not in out, out[-4000:]
-    assert r.returncode == 0, out[-4000:]
-    return out
+    return host_check.run("mirror_box_host")
 
 
 def test_no_sphere_outside_its_mirrored_box_is_hit(output):

@@ -1,33 +1,19 @@
-"""Host check of the camera-path view records (rt_api.cpp view_fill / view_record): CPU only.
-tests/native/path_host.cpp, built by tests/native/path.mk under host-side ASan + UBSan and run as a plain
+"""Host check of the camera-path view records (csrc/rt_view.h view_build / view_record behind rt_api.cpp view_fill): CPU only.
+tests/native/path_host.cpp, built by tests/native/Makefile under host-side ASan + UBSan and run as a plain
 executable, draws random scenes (0, 1, 11, 12, 64 and 65 spheres, with and without mirror planes, with and
 without a view height) and random cameras; the DevView record of each camera must equal, byte for byte, the view
 fields view_params puts into LaunchParams after rt_set_camera of that camera, and building the records must leave
 the context's camera and cached view alone."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-EXE = os.path.join(NATIVE, "build", "path_host")
+import host_check
 
 
 @pytest.fixture(scope="module")
 def output():
-    subprocess.run(["make", "-s", "-f", "path.mk", "-C", NATIVE], check=True, timeout=1800)
-    env = dict(os.environ)
-    # a preloaded library (if any) stays: ASan is told not to insist on coming first
-    env["ASAN_OPTIONS"] = ":".join(x for x in (env.get("ASAN_OPTIONS", ""), "verify_asan_link_order=0") if x)
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1"
-    r = subprocess.run([EXE], capture_output=True, text=True, timeout=300, env=env)
-    out = r.stdout + r.stderr
-    for marker in ("ERROR: AddressSanitizer", "runtime error:", "ERROR: LeakSanitizer"):
-        assert marker not in out, out[-4000:]
-    assert r.returncode == 0, out[-4000:]
-    return out
+    return host_check.run("path_host")
 
 
 def test_records_equal_the_one_camera_launch_params(output):

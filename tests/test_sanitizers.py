@@ -4,31 +4,19 @@ loop of RayTracer.cs:898-901 writes disjoint pixels, :1038), and rt_api.cpp's ho
 host-side ASan+UBSan (scene packing, view set-up and screen boxes, camera input, PPM, wire
 layout, argument checks).  CPU only: no device call is reached."""
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-BUILD = os.path.join(NATIVE, "build")
+import host_check
 
 
 @pytest.fixture(scope="module")
 def built():
-    subprocess.run(["make", "-s", "-j4", "-C", NATIVE], check=True, timeout=600)
-    return BUILD
+    return host_check.BUILD
 
 
 def _run(cmd, env_extra=None):
-    env = dict(os.environ, **(env_extra or {}))
-    # a preloaded library (if any) stays: ASan is told not to insist on coming first
-    env["ASAN_OPTIONS"] = ":".join(x for x in (env.get("ASAN_OPTIONS", ""), "verify_asan_link_order=0") if x)
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-4000:]
-    for marker in ("ERROR: AddressSanitizer", "runtime error:", "WARNING: ThreadSanitizer", "ERROR: LeakSanitizer"):
-        assert marker not in out, out[-4000:]
-    return out
+    return host_check.run(os.path.basename(cmd[0]), cmd[1:], env_extra)
 
 
 def test_oracle_asan_ubsan(built):

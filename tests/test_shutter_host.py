@@ -1,31 +1,18 @@
 """Host checks of the camera-path shutter (rt_render_shutter_bands / rt_render_shutter): CPU only.
-tests/native/shutter_host.cpp, built by tests/native/shutter.mk under host-side ASan + UBSan and run as a plain
+tests/native/shutter_host.cpp, built by tests/native/Makefile under host-side ASan + UBSan and run as a plain
 executable, checks resolve_round_n against per-channel integer arithmetic, the variant selection with a shutter
 (444 descriptors, 384 of them without one), the argument checks of both entry points on a context without devices,
 and the order of a shutter launch's view table."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-EXE = os.path.join(NATIVE, "build", "shutter_host")
+import host_check
 
 
 @pytest.fixture(scope="module")
 def output():
-    subprocess.run(["make", "-s", "-f", "shutter.mk", "-C", NATIVE], check=True, timeout=1800)
-    env = dict(os.environ)
-    # a preloaded library (if any) stays: ASan is told not to insist on coming first
-    env["ASAN_OPTIONS"] = ":".join(x for x in (env.get("ASAN_OPTIONS", ""), "verify_asan_link_order=0") if x)
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1"
-    r = subprocess.run([EXE], capture_output=True, text=True, timeout=300, env=env)
-    out = r.stdout + r.stderr
-    for marker in ("ERROR: AddressSanitizer", "runtime error:", "ERROR: LeakSanitizer"):
-        assert marker not in out, out[-4000:]
-    assert r.returncode == 0, out[-4000:]
+    out = host_check.run("shutter_host")
     assert "shutter_host: 0 failures" in out, out[-4000:]
     return out
 

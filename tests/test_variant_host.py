@@ -1,19 +1,15 @@
 """Host check of the trace kernels' variant selection (rt_internal.h pick_trace_variant): CPU only.
-tests/native/variant_host.cpp, built by tests/native/variant.mk under host-side ASan + UBSan and run as a plain
+tests/native/variant_host.cpp, built by tests/native/Makefile under host-side ASan + UBSan and run as a plain
 executable, enumerates the launch parameters the selection reads (sphere and light counts around every threshold,
 every depth class, pow, stats, output format, supersampling 0..4, camera path, frame count, copy slice, tile order
 and cost, row order and column-major) and compares each result with the rules written out as one if-chain.  The
 descriptors returned are 384, split over the kernels as the code object's are, and exactly those
 trace_variant_built admits."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NATIVE = os.path.join(ROOT, "tests", "native")
-EXE = os.path.join(NATIVE, "build", "variant_host")
+import host_check
 
 # S 7 x L 4 x a2 2 x limit 10 x pow 2 x frames 2, each with 1280 combinations of stats, format, supersampling
 # 0..4, views, copy slice, tile order, tile cost, row order and column-major.
@@ -25,17 +21,7 @@ REFUSED = 639 + 3 * 120 + 128
 
 @pytest.fixture(scope="module")
 def output():
-    subprocess.run(["make", "-s", "-f", "variant.mk", "-C", NATIVE], check=True, timeout=600)
-    env = dict(os.environ)
-    # a preloaded library (if any) stays: ASan is told not to insist on coming first
-    env["ASAN_OPTIONS"] = ":".join(x for x in (env.get("ASAN_OPTIONS", ""), "verify_asan_link_order=0") if x)
-    env["UBSAN_OPTIONS"] = "print_stacktrace=1"
-    r = subprocess.run([EXE], capture_output=True, text=True, timeout=300, env=env)
-    out = r.stdout + r.stderr
-    for marker in ("ERROR: AddressSanitizer", "runtime error:", "ERROR: LeakSanitizer"):
-        assert marker not in out, out[-4000:]
-    assert r.returncode == 0, out[-4000:]
-    return out
+    return host_check.run("variant_host")
 
 
 def test_selection_equals_the_rules_written_out(output):

@@ -25,7 +25,7 @@ TILE = 8
 
 
 def checker_basis(n):
-    """RayTracer.cs:760-765 (rt_api.cpp rt_set_scene): the checkerboard's e1, e2 of a plane normal."""
+    """RayTracer.cs:760-765 (rt_scene.h scene_build): the checkerboard's e1, e2 of a plane normal."""
     def unit(v):
         with np.errstate(invalid="ignore", divide="ignore"):
             return v / np.linalg.norm(v)

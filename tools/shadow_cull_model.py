@@ -26,7 +26,7 @@ from raytracer_hip import scenes  # noqa: E402
 
 
 def light_frame(p):
-    """rt_api.cpp rt_set_scene: the shadow-cull frame (U, V, A) of a light position."""
+    """rt_scene.h scene_build: the shadow-cull frame (U, V, A) of a light position."""
     p = np.asarray(p, dtype=np.float64)
     n = np.linalg.norm(p)
     A = p / n if n > 0 else np.array([0.0, 0.0, 1.0])

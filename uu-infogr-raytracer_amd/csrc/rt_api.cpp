@@ -23,9 +23,10 @@
 #include <vector>
 
 #include "../../include/raytracer_hip.h"
-#include "rt_dark.h"
-#include "rt_foot.h"
+#include "rt_bands.h"
 #include "rt_internal.h"
+#include "rt_scene.h"
+#include "rt_view.h"
 
 using namespace rtk;
 
@@ -223,22 +224,6 @@ struct Device {
     int comm_rank = 0, comm_world = 0;  // rt_comm_init (one rank per process); 0 = none
 };
 
-struct SceneLayout {
-    int S = 0, P = 0, L = 0, limit = 0;
-    size_t off_sph = 0, off_mat = 0, off_pl = 0, off_li = 0, off_cull = 0, off_shcull = 0, bytes = 0;
-    size_t off_shg = 0, off_shgrid = 0, off_shslab = 0, off_clus = 0, off_shpre = 0;
-    bool has_shpre = false;  // the direct kernel's shadow pre-test records (DevShadowCull [L][S + (S & 1)])
-    bool mirror_box = true;  // the direct kernel's mirrored screen boxes (view_mirror_boxes); RT_MIRROR_BOX=0: off
-    bool prim_foot = true;   // the direct kernel's plane footprints (rt_foot.h, view_fill); RT_PRIM_FOOT=0: off
-    int n_clus = 0;  // DevCluster records (the bundle kernel's per-lane pre-cull), 0: none
-    bool has_shcull = false;
-    bool has_shg = false;  // per-light shadow grids (DevShadowGrid) for the merged shadow pass
-    std::vector<unsigned char> host_blob;  // the uploaded scene image (host tests read the tables)
-    bool generic_pow = false;        // a specular material with n not in {0.5, 1, 2}
-    bool lights_a2_ok = true;        // every light's 2a = 2 p.p finite and > 0
-    std::vector<DevSphere> host_sph;  // for the per-frame primary constants
-    std::vector<DevPlane> host_pl;    // for the single-frame launches' row order (row_order)
-};
 }  // namespace
 
 // rt_render_async's frames in flight per worker behind the copy engine (rt_create_ex; RT_TICK_INFLIGHT)
@@ -389,285 +374,14 @@ void end_timed(Device& d, bool timed) {
     if (timed) (void)hipEventRecord(d.pending.back().b, d.stream);
 }
 
-// Host-side Vector3 helpers (binary32, no contraction: built with -ffp-contract=off).
-struct H3 {
-    float x, y, z;
-};
-H3 h3(rt_vec3 v) { return H3{v.x, v.y, v.z}; }
-float hdot(H3 a, H3 b) { return ((a.x * b.x) + (a.y * b.y)) + (a.z * b.z); }
-H3 hcross(H3 l, H3 r) {
-    return H3{(l.y * r.z) - (l.z * r.y), (l.z * r.x) - (l.x * r.z), (l.x * r.y) - (l.y * r.x)};
+// The view part of lp for `cam` on a W x VH frame of the context's scene (rt_view.h view_build).  view_params (the
+// context's camera, by value in the kernarg block) and the camera-path calls (one DevView per frame, view_record)
+// both build their views here, so a path frame carries the values a one-camera launch would.
+int view_fill(rt_ctx* ctx, const rt_camera& cam, int W, int VH, LaunchParams& lp) {
+    const int rc = view_build(ctx->layout, cam, W, VH, lp);
+    if (rc != RT_OK) return fail(ctx, rc, "invalid frame size %dx%d", W, VH);
+    return RT_OK;
 }
-H3 hnormalize(H3 a) {
-    float s = 1.0f / std::sqrt(hdot(a, a));
-    return H3{a.x * s, a.y * s, a.z * s};
-}
-bool hzero(rt_vec3 v) { return v.x == 0 && v.y == 0 && v.z == 0; }
-
-DevMaterial dev_material(const rt_material& m, rt_vec3 ambient) {
-    DevMaterial d;
-    std::memset(&d, 0, sizeof d);
-    d.kd[0] = m.kd.x, d.kd[1] = m.kd.y, d.kd[2] = m.kd.z;
-    d.amb[0] = ambient.x * m.ka.x, d.amb[1] = ambient.y * m.ka.y, d.amb[2] = ambient.z * m.ka.z;
-    d.ks[0] = m.ks.x, d.ks[1] = m.ks.y, d.ks[2] = m.ks.z;
-    d.n = m.n;
-    d.km[0] = m.km.x, d.km[1] = m.km.y, d.km[2] = m.km.z;
-    d.flags = (hzero(m.km) ? 0u : MAT_MIRROR) | (hzero(m.kd) ? 0u : MAT_DIFFUSE) |
-              ((!hzero(m.ks) && m.n > 0.0f) ? MAT_SPEC : 0u);
-    d.pow_kind = m.n == 1.0f ? POW_ONE : m.n == 0.5f ? POW_HALF : m.n == 2.0f ? POW_TWO : POW_GENERIC;
-    return d;
-}
-
-// Shadow rays (IntersectShadowLight, RayTracer.cs:573-582 -> IntersectsSphere with epsilon
-// 0.001f, :613-636): with 2a finite and > 0 the ray collides iff fl(fl(n / 2a) - e) > 0, n =
-// fl(-b - sqrt(disc)) (the near root decides, rt_kernel.hip shadow_blocked).  For floats q and
-// e the sign of fl(q - e) is that of q - e, so the test is fl(n / 2a) > e.  Correct rounding is
-// monotonic: fl(z) > e iff z > m, m = e + ulp(e)/2 the midpoint above e, except z == m, which
-// rounds to the even neighbour -- succ(e) when e's significand is odd.  So the collision is
-// n >= m * 2a (odd e) or n > m * 2a (even e); m has 25 significant bits and 2a 24, so the
-// product is exact in double, and for a float n, "n >= T" equals "n >= the smallest float >= T"
-// (and "n > T" equals "n >= the smallest float > T").  Returns that float (+inf above FLT_MAX).
-float shadow_threshold(float a2) {
-    const float e = 0.001f;
-    int ex = 0;
-    (void)std::frexp(e, &ex);                                // e = f * 2^ex, f in [0.5, 1)
-    const double m = (double)e + std::ldexp(1.0, ex - 25);  // + ulp(e) / 2 (ulp = 2^(ex - 24))
-    uint32_t eb;
-    std::memcpy(&eb, &e, sizeof eb);
-    const bool odd = (eb & 1u) != 0;
-    const double T = m * (double)a2;                         // exact
-    float t = (float)T;
-    if ((double)t < T || (!odd && (double)t == T)) t = std::nextafter(t, INFINITY);
-    return t;
-}
-
-int total_bands(int H, int band_rows) { return (H + band_rows - 1) / band_rows; }
-int bands_of(int H, int band_rows, int first, int step) {
-    int tb = total_bands(H, band_rows);
-    return first < tb ? (tb - 1 - first) / step + 1 : 0;
-}
-// Bytes of one frame's output of a band render in `fmt`.
-size_t band_output_bytes(int W, int H, int nb, int band_rows, int fmt) {
-    return fmt == RT_BANDS_FRAME ? (size_t)W * H * 4 : (size_t)nb * band_rows * W * (fmt == RT_BANDS_RGB24 ? 3 : 4);
-}
-
-// Conservative screen box of a sphere for primary rays (culling only; computed in double).
-//
-// Pixel (x, y) traces the line from the camera along D = R lx + U ly + F lz with
-// lx = (x/W - 0.5) pw, ly = (y/H - 0.5) ph, lz = near (TracePixel :963-971).  By the
-// cull_mask analysis the binary32 IntersectsSphere cannot select the sphere when that line
-// passes at distance >= rho = r (1 + 2^-8) + 2^-8 |u| from its centre (u = C - camera), with
-// |u| also scaled by the kernel's direction error (cancellation in vp - cam, bounded by
-// 2^-20 (|cam| + |D|) / |D|; no box when that exceeds 2^-12).  The distance to the line is at
-// least the distance to the plane through it containing the camera's up (right) axis, so
-// in camera coordinates (cx, cy, cz) the x range follows from the 2-D circle (cx, cz; rho):
-// lx / lz in [tan(phi - g), tan(phi + g)], phi = atan2(cx, cz), g = asin(rho / |(cx, cz)|),
-// valid when cz > rho (sphere strictly in front); same for y with (cy, cz).  Two pixels of
-// slack cover the binary32 pixel-to-direction mapping and the basis' non-orthogonality.
-// extra: added to rho (the mirrored boxes' allowances, mirror_boxes; 0 for the primary boxes).
-PrimBox prim_box(const LaunchParams& lp, const DevSphere& s, double extra = 0.0) {
-    const PrimBox all{INT_MIN / 2, INT_MAX / 2, INT_MIN / 2, INT_MAX / 2};
-    const double pw = lp.pw, ph = lp.ph, lz = lp.nearc;
-    if (!(pw > 0) || !(ph > 0) || !(lz > 0) || !std::isfinite(pw) || !std::isfinite(ph) || !std::isfinite(lz))
-        return all;
-    const double cam[3] = {lp.cam[0], lp.cam[1], lp.cam[2]};
-    const double u[3] = {s.cx - cam[0], s.cy - cam[1], s.cz - cam[2]};
-    auto dot3 = [](const double* a, const float* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
-    const double ulen = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    const double camlen = std::sqrt(cam[0] * cam[0] + cam[1] * cam[1] + cam[2] * cam[2]);
-    const double dmax = std::sqrt(0.25 * pw * pw + 0.25 * ph * ph + lz * lz);
-    const double dir_err = 0x1p-20 * (camlen + dmax) / lz + 0x1p-20;
-    const double r = std::sqrt((double)s.r2);
-    if (!std::isfinite(ulen) || !std::isfinite(r) || !(dir_err <= 0x1p-12)) return all;
-    const double rho = (r * (1.0 + 0x1p-8) + (0x1p-8 + 0x1p-20 + dir_err) * ulen) * (1.0 + 0x1p-16) + 0x1p-60 + extra;
-    auto fdot = [](const float* a, const float* b) { return (double)a[0] * b[0] + (double)a[1] * b[1] + (double)a[2] * b[2]; };
-    const double ortho = std::fabs(fdot(lp.right, lp.up)) + std::fabs(fdot(lp.right, lp.fwd)) +
-                         std::fabs(fdot(lp.up, lp.fwd)) + std::fabs(fdot(lp.right, lp.right) - 1.0) +
-                         std::fabs(fdot(lp.up, lp.up) - 1.0) + std::fabs(fdot(lp.fwd, lp.fwd) - 1.0);
-    if (!(ortho < 0x1p-18)) return all;  // the camera basis is orthonormal up to rounding
-    const double cx = dot3(u, lp.right), cy = dot3(u, lp.up), cz = dot3(u, lp.fwd);
-    if (!(cz > rho * (1.0 + 0x1p-10))) return all;
-    auto range = [&](double c, double plane, int n, int& lo, int& hi) {
-        const double phi = std::atan2(c, cz);
-        const double g = std::asin(std::min(1.0, rho / std::sqrt(c * c + cz * cz)));
-        const double tlo = std::tan(phi - g), thi = std::tan(phi + g);
-        const double flo = n * (0.5 + lz * tlo / plane), fhi = n * (0.5 + lz * thi / plane);
-        if (!std::isfinite(flo) || !std::isfinite(fhi)) {
-            lo = INT_MIN / 2, hi = INT_MAX / 2;
-            return;
-        }
-        lo = (int)std::max(-1e9, std::floor(flo) - 2.0);
-        hi = (int)std::min(1e9, std::ceil(fhi) + 2.0);
-    };
-    PrimBox b;
-    range(cx, pw, lp.W, b.x0, b.x1);
-    range(cy, ph, lp.H, b.y0, b.y1);
-    return b;
-}
-
-// Mirrored screen boxes (LaunchParams::mbox; the direct kernel's first reflected segment; culling only).
-//
-// A ray reflected by the plane q = {x : n.x = cn} extends backwards through the camera's mirror image, so the
-// reflected line of pixel (x, y) passes sphere i (centre C) at the distance at which the pixel's primary line,
-// continued through q, passes the mirrored centre C' = C - 2 n (n.C - cn) / n.n.  The box is prim_box of (C', r)
-// with rho grown by `extra`, which covers what the binary32 chain adds between the two lines for a lane whose
-// primary hit on q has t <= t_max (eps = 2^-24, E the camera, |d| <= 1 + 2^-20, U = |E| + |cn| / |n| + 2 t_max):
-//   * hp = fl(E + fl(d t)) lies within dh = 4 eps U of the primary line (two roundings per component);
-//   * hp lies within dp = 16 eps U + dh of q: with t = fl(num_f / den_f), n.(E + d t) - cn = t (den - den_f) +
-//     (num_f - num) + the quotient's rounding t eps den_f exactly (no first-order step: a grazing den does not
-//     matter), num_f and den_f each three products and three sums of terms bounded by |E| |n| + |cn| and |d| |n|;
-//     mirroring about the plane through hp instead of q moves C' by 2 dp;
-//   * the binary32 reflection d' = fl(d - n fl(2 fl(d.n))) mirrored back differs from d by at most
-//     2 |n.n - 1| + 12 eps <= 2^-18 (the reference reflects about the raw normal: |n.n - 1| <= 2^-20 is required),
-//     an angle below 2^-16, which moves the line by at most 2^-16 |C' - hp| at C';
-//   * the cull rule itself (rt_kernel.hip, "Wave-level ray bundles": not selectable when the line passes C at
-//     r (1 + 2^-8) + 2^-8 |C - hp| or more) asks for 2^-8 |C - hp|, and |C - hp| <= |C' - E| + |hp - E| + 2 dp
-//     with |hp - E| <= 1.001 t_max; prim_box supplies the 2^-8 |C' - E| part.
-// t_max = MIRROR_TMAX_FACTOR max_i (|C'_i - E| + r_i): the 2^-8 t_max term grows every box in proportion to t_max,
-// while the lanes beyond it (full test) lie within atan(h / t_max) of the plane's horizon, in inverse proportion.
-// A host model of C3's 1080p frame (8x8 tiles, these boxes) counts the sphere pairs a wave's first reflected
-// segment runs, 4 without boxes: 0.92 at factor 0.5, 0.78 at 1, 0.75 at 1.5 and at 2, 0.78 at 3, 0.83 at 4, 0.99
-// at 8 -- a flat optimum; 2 (two tile rows under the horizon take the full test, rho grows by 0.8 % of the
-// farthest mirrored sphere's distance).  No table (the plane's lanes take every sphere) when |n.n - 1| > 2^-20, an input is not finite, or
-// no sphere has a usable record; a sphere with r^2 < 2^-100 or |C' - E| + t_max > 2^40 keeps the box "all" (the
-// cull rule's own domain), as does one that fails prim_box's preconditions.
-// margins = false (the host check's teeth, tests/native/mirror_box_host.cpp): extra = 0 and no t_max.
-constexpr double MIRROR_TMAX_FACTOR = 2.0;
-bool mirror_boxes(const LaunchParams& lp, const DevPlane& q, const std::vector<DevSphere>& sph, PrimBox* box,
-                  float* t_max_out, bool margins = true, double tmax_factor = MIRROR_TMAX_FACTOR) {
-    const PrimBox all{INT_MIN / 2, INT_MAX / 2, INT_MIN / 2, INT_MAX / 2};
-    const size_t S = sph.size();
-    for (size_t i = 0; i < S; ++i) box[i] = all;
-    const double n[3] = {q.nx, q.ny, q.nz}, E[3] = {lp.cam[0], lp.cam[1], lp.cam[2]}, cn = q.cn;
-    const double nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
-    if (!(std::fabs(nn - 1.0) <= 0x1p-20) || !std::isfinite(cn)) return false;
-    const double elen = std::sqrt(E[0] * E[0] + E[1] * E[1] + E[2] * E[2]);
-    if (!std::isfinite(elen)) return false;
-    std::vector<DevSphere> mir(S);
-    std::vector<double> ulen(S);
-    double far = 0.0;
-    for (size_t i = 0; i < S; ++i) {
-        const double C[3] = {sph[i].cx, sph[i].cy, sph[i].cz};
-        const double k = 2.0 * (n[0] * C[0] + n[1] * C[1] + n[2] * C[2] - cn) / nn;
-        const double M[3] = {C[0] - k * n[0], C[1] - k * n[1], C[2] - k * n[2]};
-        // the mirrored centre as floats (prim_box reads a DevSphere); its rounding, <= 2 eps |C'|, goes into extra
-        mir[i] = DevSphere{(float)M[0], (float)M[1], (float)M[2], sph[i].r2};
-        const double u[3] = {M[0] - E[0], M[1] - E[1], M[2] - E[2]};
-        ulen[i] = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-        const double reach = ulen[i] + std::sqrt((double)sph[i].r2);
-        if (std::isfinite(reach)) far = std::max(far, reach);
-    }
-    const double t_max = margins ? tmax_factor * far : (double)INFINITY;
-    if (margins && !(t_max > 0.0 && t_max <= 0x1p40)) return false;
-    const double eps = 0x1p-24;
-    const double U = elen + std::fabs(cn) / std::sqrt(nn) + 2.0 * t_max;
-    const double dh = 4.0 * eps * U, dp = 16.0 * eps * U + dh;
-    for (size_t i = 0; i < S; ++i) {
-        if (!std::isfinite(ulen[i]) || !(sph[i].r2 >= 0x1p-100f)) continue;
-        double extra = 0.0;
-        if (margins) {
-            if (!(ulen[i] + t_max <= 0x1p40)) continue;
-            const double mlen = std::sqrt((double)mir[i].cx * mir[i].cx + (double)mir[i].cy * mir[i].cy + (double)mir[i].cz * mir[i].cz);
-            extra = 0x1p-8 * (1.001 * t_max + 2.0 * dp) + dh + 2.0 * dp + 0x1p-16 * (ulen[i] + 1.001 * t_max + 2.0 * dp) +
-                    2.0 * eps * mlen * (1.0 + 0x1p-8);
-            extra *= 1.0 + 0x1p-10;
-        }
-        box[i] = prim_box(lp, mir[i], extra);
-    }
-    // (the largest float not above t_max: a lane compares its binary32 t against it)
-    float tm = margins ? (float)t_max : INFINITY;
-    if (margins && (double)tm > t_max) tm = std::nextafter(tm, 0.0f);
-    *t_max_out = tm;
-    return true;
-}
-
-// The tables of a view: the first MIRROR_BOX_PLANES planes with a mirror material, those whose table can be built.
-void view_mirror_boxes(LaunchParams& lp, const SceneLayout& L) {
-    lp.mbox_n = 0;
-    for (int k = 0; k < MIRROR_BOX_PLANES; ++k) {
-        lp.mbox_plane[k] = -1, lp.mbox_tmax[k] = 0.0f;
-        for (int i = 0; i < CULL_MIN_SPHERES; ++i) lp.mbox[k][i] = PrimBox{INT_MIN / 2, INT_MAX / 2, INT_MIN / 2, INT_MAX / 2};
-    }
-    if (!L.mirror_box || !lp.prim_const || L.S < 1 || L.S >= CULL_MIN_SPHERES || L.limit < 1) return;
-    if (L.host_blob.size() < L.off_mat + sizeof(DevMaterial) * (size_t)(L.S + L.P)) return;
-    const DevMaterial* mat = (const DevMaterial*)(L.host_blob.data() + L.off_mat);
-    int mirrors = 0;
-    for (int j = 0; j < L.P && mirrors < MIRROR_BOX_PLANES; ++j) {
-        if (!(mat[L.S + j].flags & MAT_MIRROR)) continue;
-        ++mirrors;
-        const int k = lp.mbox_n;
-        if (mirror_boxes(lp, L.host_pl[(size_t)j], L.host_sph, lp.mbox[k], &lp.mbox_tmax[k])) {
-            lp.mbox_plane[k] = j;
-            ++lp.mbox_n;
-        }
-    }
-}
-
-// Order of a single-frame launch's tile rows (LaunchParams::row_order). The launch's last waves set
-// its tail, so the expensive rows should start first and the cheap ones come last.  A tile row's cost
-// is estimated from eight primary rays through its middle pixel row: 1 for a ray that meets nothing,
-// 1 + L when it meets a plane in front of the camera or falls inside a diffuse sphere's screen box
-// (prim_box: shaded, with shadow rays), (1 + L)(1 + min(limit, 4)) inside a mirror sphere's box (its
-// reflected chain is shaded too).  Rows are sorted by decreasing estimate, ties in natural order.
-// The estimate only orders the workgroups: every tile is traced exactly as before.
-int row_order(const LaunchParams& lp, const SceneLayout& L, uint16_t* order) {
-    const int rows = (lp.H + 7) / 8;
-    if (rows < 2 || rows > ROW_ORDER_MAX) return 0;
-    const DevMaterial* mat = L.host_blob.size() >= L.off_mat + sizeof(DevMaterial) * (size_t)(L.S + L.P)
-                                 ? (const DevMaterial*)(L.host_blob.data() + L.off_mat)
-                                 : nullptr;
-    const double shade = 1.0 + L.L, mirror = shade * (1.0 + std::min(L.limit, 4));
-    std::vector<double> cost((size_t)rows, 0.0);
-    for (int r = 0; r < rows; ++r) {
-        const int y = std::min(lp.H - 1, r * 8 + 4);
-        const double ly = ((double)y / lp.H - 0.5) * lp.ph;
-        for (int j = 0; j < 8; ++j) {
-            const int x = (int)(((2 * j + 1) * (long long)lp.W) / 16);
-            const double lx = ((double)x / lp.W - 0.5) * lp.pw;
-            double d[3];
-            for (int k = 0; k < 3; ++k) d[k] = lp.right[k] * lx + lp.up[k] * ly + lp.fwd[k] * lp.nearc;
-            double w = 1.0;
-            for (const DevPlane& q : L.host_pl) {
-                const double den = d[0] * q.nx + d[1] * q.ny + d[2] * q.nz;
-                const double num = q.cn - (lp.cam[0] * q.nx + lp.cam[1] * q.ny + lp.cam[2] * q.nz);
-                if (den != 0 && num / den > 0) w = std::max(w, shade);
-            }
-            if (lp.prim_const)
-                for (int i = 0; i < L.S; ++i)
-                    if (x >= lp.pbox[i].x0 && x <= lp.pbox[i].x1 && y >= lp.pbox[i].y0 && y <= lp.pbox[i].y1)
-                        w = std::max(w, mat && (mat[i].flags & MAT_MIRROR) ? mirror : shade);
-            cost[(size_t)r] += w;
-        }
-    }
-    std::vector<int> idx((size_t)rows);
-    for (int r = 0; r < rows; ++r) idx[(size_t)r] = r;
-    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return cost[(size_t)a] > cost[(size_t)b]; });
-    for (int r = 0; r < rows; ++r) order[r] = (uint16_t)idx[(size_t)r];
-    return rows;
-}
-
-void copy_view(const LaunchParams& from, LaunchParams& to) {
-    std::memcpy(to.cam, from.cam, sizeof to.cam);
-    std::memcpy(to.right, from.right, sizeof to.right);
-    std::memcpy(to.up, from.up, sizeof to.up);
-    std::memcpy(to.fwd, from.fwd, sizeof to.fwd);
-    to.pw = from.pw, to.ph = from.ph, to.nearc = from.nearc;
-    to.W = from.W, to.H = from.H;
-    to.prim_const = from.prim_const;
-    std::memcpy(to.pc, from.pc, sizeof to.pc);
-    std::memcpy(to.pbox, from.pbox, sizeof to.pbox);
-    to.mbox_n = from.mbox_n;
-    std::memcpy(to.mbox_plane, from.mbox_plane, sizeof to.mbox_plane);
-    std::memcpy(to.mbox_tmax, from.mbox_tmax, sizeof to.mbox_tmax);
-    std::memcpy(to.mbox, from.mbox, sizeof to.mbox);
-    to.foot_n = from.foot_n;
-    std::memcpy(to.foot, from.foot, sizeof to.foot);
-    to.row_order_n = from.row_order_n;
-    to.col_major = from.col_major;
-    std::memcpy(to.row_order, from.row_order, sizeof(uint16_t) * (size_t)from.row_order_n);
-}
-
-int view_fill(rt_ctx* ctx, const rt_camera& cam, int W, int VH, LaunchParams& lp);
 
 // The view of a W x VH frame (VH: rt_set_view_height, else H), of which a render traces rows [0, H).
 // ss > 0 (supersampling, log2 of the factor): W and H arrive in samples, and so does the view height here.
@@ -687,57 +401,6 @@ int view_params(rt_ctx* ctx, int W, int H, LaunchParams& lp, int ss = 0) {
     copy_view(lp, ctx->view_lp);
     ctx->view_cam = ctx->cam, ctx->view_w = W, ctx->view_h = VH, ctx->view_rows = H, ctx->view_ok = true;
     return RT_OK;
-}
-
-// Everything of a W x VH view that depends on the camera, into the view part of lp: position and basis, the
-// view plane (pw, ph, nearc: the same for every camera of one frame size), lp.W / lp.H = the view's size, the
-// primary constants and screen boxes (prim_box), the mirrored boxes (view_mirror_boxes) and the plane footprints
-// (rt_foot.h foot_build; a DevView record carries none: view_record).  view_params (the
-// context's camera, by value in the kernarg block) and the camera-path calls (one DevView per frame,
-// view_record) both build their views here, so a path frame carries the values a one-camera launch would.
-int view_fill(rt_ctx* ctx, const rt_camera& cam, int W, int VH, LaunchParams& lp) {
-    rt_view v;
-    int rc = rt_camera_view(&cam, W, VH, &v);
-    if (rc != RT_OK) return fail(ctx, rc, "invalid frame size %dx%d", W, VH);
-    lp.cam[0] = v.position.x, lp.cam[1] = v.position.y, lp.cam[2] = v.position.z;
-    lp.right[0] = v.right.x, lp.right[1] = v.right.y, lp.right[2] = v.right.z;
-    lp.up[0] = v.up.x, lp.up[1] = v.up.y, lp.up[2] = v.up.z;
-    lp.fwd[0] = v.forward.x, lp.fwd[1] = v.forward.y, lp.fwd[2] = v.forward.z;
-    lp.pw = v.plane_width, lp.ph = v.plane_height, lp.nearc = v.near_clip;
-    lp.W = W, lp.H = VH;  // (the screen boxes and the row order in the view's pixels)
-    // primary-segment sphere constants (origin = camera for every pixel)
-    const std::vector<DevSphere>& sph = ctx->layout.host_sph;
-    lp.prim_const = sph.size() <= (size_t)MAX_PRIM_CONST ? 1 : 0;
-    if (lp.prim_const)
-        for (size_t i = 0; i < sph.size(); ++i) {
-            const H3 oc{lp.cam[0] - sph[i].cx, lp.cam[1] - sph[i].cy, lp.cam[2] - sph[i].cz};
-            lp.pc[i] = PrimConst{oc.x, oc.y, oc.z, hdot(oc, oc) - sph[i].r2};
-            lp.pbox[i] = prim_box(lp, sph[i]);
-        }
-    view_mirror_boxes(lp, ctx->layout);  // (lp.H = VH: in the view's pixels, like pbox)
-    // plane footprints (rt_foot.h): with the screen boxes they tell a wave that no primary ray of its tile hits anything
-    const std::vector<DevPlane>& pl = ctx->layout.host_pl;
-    std::memset(lp.foot, 0, sizeof lp.foot);
-    lp.foot_n = ctx->layout.prim_foot && lp.prim_const && pl.size() <= (size_t)FOOT_MAX
-                    ? foot_build(lp, pl.data(), (int)pl.size(), lp.foot)
-                    : -1;
-    return RT_OK;
-}
-
-// The DevView record of a view built by view_fill (padding zeroed: records compare bytewise).
-void view_record(const LaunchParams& lp, DevView& v) {
-    std::memset(&v, 0, sizeof v);
-    std::memcpy(v.cam, lp.cam, sizeof v.cam);
-    std::memcpy(v.right, lp.right, sizeof v.right);
-    std::memcpy(v.up, lp.up, sizeof v.up);
-    std::memcpy(v.fwd, lp.fwd, sizeof v.fwd);
-    v.prim_const = lp.prim_const;
-    v.mbox_n = lp.mbox_n;
-    std::memcpy(v.mbox_plane, lp.mbox_plane, sizeof v.mbox_plane);
-    std::memcpy(v.mbox_tmax, lp.mbox_tmax, sizeof v.mbox_tmax);
-    std::memcpy(v.pc, lp.pc, sizeof v.pc);
-    std::memcpy(v.pbox, lp.pbox, sizeof v.pbox);
-    std::memcpy(v.mbox, lp.mbox, sizeof v.mbox);
 }
 
 void scene_params(const rt_ctx* ctx, const Device& d, LaunchParams& lp) {
@@ -760,23 +423,14 @@ void scene_params(const rt_ctx* ctx, const Device& d, LaunchParams& lp) {
     lp.counters = ctx->counting ? d.d_counters : nullptr;  // nullptr: the kernels count nothing (rt_set_counting)
 }
 
-// Per-column / per-row view-plane coordinates of TracePixel (:963-965), computed with the
-// same binary32 operations as the kernel would (-ffp-contract=off, correctly rounded
-// division): lx[x] = ((float)x / W - 0.5f) * pw, ly[y] = ((float)y / H - 0.5f) * ph.
-// Rebuilt only when the frame size or view-plane size changes; frames in flight may read
+// Per-column / per-row view-plane coordinates of TracePixel (:963-965) on the device (rt_view.h
+// view_table_values: lx[W] then ly[VH]).  Rebuilt only when the frame size or view-plane size changes; frames in flight may read
 // the old table, so the device is synchronised first.
 int view_tables(rt_ctx* ctx, Device& d, LaunchParams& lp, int ss = 0) {
     const int VH = ctx->view_height > 0 ? ctx->view_height << ss : lp.H;  // the view's height (ly of row y)
     if (d.tab_w != lp.W || d.tab_h != VH || d.tab_pw != lp.pw || d.tab_ph != lp.ph || !d.d_view_tab) {
         std::vector<float> t((size_t)lp.W + (size_t)VH);
-        for (int x = 0; x < lp.W; ++x) {
-            const float px = (float)x / (float)lp.W - 0.5f;
-            t[(size_t)x] = px * lp.pw;
-        }
-        for (int y = 0; y < VH; ++y) {
-            const float py = (float)y / (float)VH - 0.5f;
-            t[(size_t)lp.W + (size_t)y] = py * lp.ph;
-        }
+        view_table_values(lp.W, VH, lp.pw, lp.ph, t.data());
         HIP_TRY(ctx, hipDeviceSynchronize());
         int rc = grow(ctx, (void**)&d.d_view_tab, &d.view_tab_cap, t.size() * sizeof(float));
         if (rc != RT_OK) return rc;
@@ -874,23 +528,6 @@ bool order_begin(Device& d, int cand, hipStream_t s) {
 }
 
 void order_end(Device& d, hipStream_t s) { (void)hipEventRecord(d.order.pending.back().b, s); }
-
-// The measured tile order: tiles 0..n-1 (row-major, tx per row) by decreasing cost, ties in natural order, as
-// ty << 16 | tx entries.  A stable counting sort in 16-tick (160 ns) buckets (wider ones past 2^20 ticks): linear
-// in the tile count -- an 8K frame's 518,400 tiles sort in a few ms, once per measuring round.
-void tiles_by_cost(const uint32_t* cost, size_t n, uint32_t tx, uint32_t* order) {
-    uint32_t cmax = 0;
-    for (size_t i = 0; i < n; ++i) cmax = std::max(cmax, cost[i]);
-    const int shift = cmax >> 4 < (1u << 16) ? 4 : 4 + (32 - __builtin_clz(cmax >> 20 | 1u));
-    const size_t nb = (size_t)(cmax >> shift) + 1;
-    std::vector<uint32_t> start(nb + 1, 0);
-    for (size_t i = 0; i < n; ++i) start[nb - (cost[i] >> shift)]++;  // bucket 0 = the longest
-    for (size_t b = 1; b <= nb; ++b) start[b] += start[b - 1];
-    for (size_t i = 0; i < n; ++i) {
-        const uint32_t t = (uint32_t)i;
-        order[start[nb - 1 - (cost[i] >> shift)]++] = (t / tx) << 16 | (t % tx);
-    }
-}
 
 // Candidate 3 of a single-frame launch (the direct kernel's 4-tile workgroups): the first launch of each
 // measuring round (and of each frame size / scene) records every tile's duration instead of being timed as a
@@ -1109,45 +746,6 @@ int32_t* mapped_host(const rt_ctx* ctx, int g, void* host, size_t bytes) {
     return nullptr;
 }
 
-// The band pipeline of the Tick (the reference's only parallel loop is the row-parallel
-// one of RayTracer.cs:898-901).  Worker g of n (a device; RT_CREATE_SHARED_DEVICE: a stream of one
-// device) traces the interleaved 8-row bands b = g, g + n, ... of the frame (n == 1: the frame as one
-// band) -- balanced however the scene's cost is spread over the rows (the top ~45 % of C2 is sky) --
-// packed band after band, and hands them to the caller's frame itself.
-constexpr int TICK_BAND_ROWS = 8;
-static_assert(TICK_BAND_ROWS % 8 == 0, "the Tick's bands hold whole tiles of an adaptive launch (adaptive_band_ok)");
-struct Share {
-    int band_rows, first, step, nb;  // bands (first, step) of band_rows rows, nb of them
-    size_t words;                    // int32 of the packed band set inside the frame (a cut last band)
-};
-// The int32 of bands [k0, k1) of a share (the frame's last band may be cut at H).
-size_t share_words(const Share& sh, int W, int H, int k0, int k1) {
-    size_t rows = 0;
-    for (int k = k0; k < k1; ++k) {
-        const long long y0 = (long long)(sh.first + (long long)k * sh.step) * sh.band_rows;
-        rows += (size_t)std::max(0LL, std::min<long long>(sh.band_rows, (long long)H - y0));
-    }
-    return rows * (size_t)W;
-}
-Share share_of(int W, int H, int g, int n, bool banded) {
-    Share sh;
-    sh.band_rows = (n == 1 && !banded) ? H : TICK_BAND_ROWS;
-    sh.first = g, sh.step = n;
-    sh.nb = bands_of(H, sh.band_rows, g, n);
-    sh.words = share_words(sh, W, H, 0, sh.nb);
-    return sh;
-}
-// Where band k of a share starts in the frame, in int32.
-size_t band_word0(const Share& sh, int W, int k) {
-    return (size_t)(sh.first + (size_t)k * sh.step) * (size_t)sh.band_rows * (size_t)W;
-}
-// Bands [k0, k1) of chunk c of nc of a share (none when the share has fewer bands than chunks).
-struct Bands {
-    int k0, k1;
-};
-Bands chunk_bands(const Share& sh, int c, int nc) {
-    return Bands{(int)((long long)sh.nb * c / nc), (int)((long long)sh.nb * (c + 1) / nc)};
-}
 // The trace of bands [k0, k1) of a share into the packed band set at buf (band 0); `slice` rides in the launch.
 TraceReq share_req(const Share& sh, int W, int H, int k0, int k1, int32_t* buf, const CopyJob* slice = nullptr) {
     TraceReq q{W, H, sh.band_rows, sh.first + k0 * sh.step, sh.step, buf + (size_t)k0 * sh.band_rows * W};
@@ -1155,41 +753,6 @@ TraceReq share_req(const Share& sh, int W, int H, int k0, int k1, int32_t* buf, 
     q.max_bands = k1 - k0;
     return q;
 }
-// The hand-off of bands [k0, k1) of a share, traced at src (packed from band k0), into the frame whose
-// row 0 is at `frame` (a device-mapped host address or device memory of this worker).
-CopyJob share_job(const Share& sh, int W, int H, int k0, int k1, const int32_t* src, int32_t* frame) {
-    CopyJob j{};
-    const size_t bw = (size_t)sh.band_rows * (size_t)W;
-    j.src = src;
-    j.dst = frame + band_word0(sh, W, k0);
-    j.words = share_words(sh, W, H, k0, k1);
-    j.band_words = sh.step == 1 ? 0u : (unsigned)bw;  // one worker: the bands are one contiguous run
-    j.dst_stride = (unsigned long long)sh.step * bw;
-    return j;
-}
-
-// The copies that hand bands [k0, k1) of a share, packed from band 0, to a frame, each as fn(dst, src, width,
-// rows, pitch) in int32: `rows` runs of `width`, packed at src, to dst + r * pitch in the frame (pitch 0: one
-// run, a plain copy).  One contiguous run (one worker), a pitched copy over the whole bands plus the frame's
-// cut last band (a registered, pinned frame: the copy engine writes the rows in place), or one run per band (an
-// unregistered frame -- the slow path; callers register Surface.pixels once -- where a pitched copy would be
-// staged).  fn returns RT_OK to go on.
-template <class Fn>
-int for_band_copies(const Share& sh, int W, int H, int k0, int k1, bool pinned, Fn&& fn) {
-    if (k1 <= k0) return RT_OK;
-    const size_t bw = (size_t)sh.band_rows * (size_t)W;
-    auto run = [&](int k, int n) { return fn(band_word0(sh, W, k), (size_t)k * bw, share_words(sh, W, H, k, k + n), 1, 0); };
-    if (sh.step == 1) return run(k0, k1 - k0);
-    if (pinned) {
-        const bool cut = share_words(sh, W, H, k1 - 1, k1) < bw;
-        const int full = k1 - k0 - (cut ? 1 : 0);
-        if (full > 0) RT_TRY(fn(band_word0(sh, W, k0), (size_t)k0 * bw, bw, (size_t)full, (size_t)sh.step * bw));
-        return cut ? run(k1 - 1, 1) : RT_OK;
-    }
-    for (int k = k0; k < k1; ++k) RT_TRY(run(k, 1));
-    return RT_OK;
-}
-
 // Issue each worker's pending rt_render_async hand-off (the last frame's D2H) on its async stream.
 int flush_hand(rt_ctx* ctx) {
     if (!ctx) return RT_OK;
@@ -1452,244 +1015,6 @@ void rt_destroy(rt_ctx* ctx) {
     delete ctx;
 }
 
-namespace {
-// Light frame in double (the DevLight frame is its binary32 rounding).
-struct Frame3 {
-    double U[3], V[3], A[3];
-};
-
-// The lowest value x (double) that binary32 fma(x, s, o) can map to a value >= k (k integer): every
-// x_f with floor(fl(x_f * s + o)) == k satisfies x_f >= cell_lo(k, s, o), and every x_f with that
-// floor <= k - 1 satisfies x_f < cell_lo(k, s, o)... up to the allowance eps_k (a relative 2^-24 of
-// the fma result plus double rounding here, taken 4x).  s > 0.
-double cell_lo(int k, float s, float o) { return ((double)k - 0x1p-22 * (std::fabs((double)k) + 2.0) - (double)o) / (double)s; }
-double cell_hi(int k, float s, float o) {  // the highest x that can map to k (exclusive bound of k + 1)
-    return ((double)(k + 1) + 0x1p-22 * (std::fabs((double)k + 1.0) + 2.0) - (double)o) / (double)s;
-}
-float down(double v) { float f = (float)v; return (double)f > v ? std::nextafter(f, -INFINITY) : f; }
-float up(double v) { float f = (float)v; return (double)f < v ? std::nextafter(f, INFINITY) : f; }
-
-// The direct kernel's shadow pre-test records (rt_kernel.hip shadow_pre_keep; culling only).  The kernel drops
-// sphere i for a lane's shadow ray toward light l only under shadow_sphere_cull's rules for a single ray (R = 0)
-// from the lane's hit point O: w = C - O in the light's frame, margin 2^-8 dc + 2^-18 |O| with dc >= |C - O|,
-// line miss if w_u^2 + w_v^2 > (r' + 2^-18 |C| + margin)^2, behind if -w_a > margin.  Here dc is bounded by
-// |O_f|_1 + |C_f|_1 (frame coordinates), so the margin splits into a lane part m_l = 2^-8 (1 + 2^-8) |O_f|_1 +
-// 2^-30 (kernel: it also covers the 2^-18 |O| projection allowance, and its 2^-30 floor makes every cull imply
-// |C - O| > 2^-30) and a sphere part m_c = 2^-8 (1 + 2^-20) |C_f|_1, folded in here: ca' = ca + m_c and
-// rr' = r' + 2^-18 |C| + m_c, both rounded up.  Records that allow no culling -- a light whose a = p.p is outside
-// [2^-40, 2^40] or whose 2a is not finite, a sphere without a usable cull radius (NaN, < 2^-50), |C_f|_1 >= 2^38
-// or non-finite -- get ca' = rr' = +inf (no rule can hold); the padding sphere of an odd count gets cu = +inf
-// (always dropped: it never hits).
-void build_shadow_pre(const DevLight* li, int n_lights, const DevSphereCull* cull, int n_spheres, int s_pad,
-                      DevShadowCull* out) {
-    for (int j = 0; j < n_lights; ++j) {
-        const DevLight& d = li[j];
-        const bool l_ok = d.a >= 0x1p-40f && d.a <= 0x1p40f && d.a2 > 0.0f && d.a2 < INFINITY;
-        for (int i = 0; i < s_pad; ++i) {
-            DevShadowCull& e = out[(size_t)j * (size_t)s_pad + (size_t)i];
-            if (i >= n_spheres) {
-                e = DevShadowCull{INFINITY, 0.0f, 0.0f, 0.0f};
-                continue;
-            }
-            const double c[3] = {cull[i].cx, cull[i].cy, cull[i].cz};
-            const double clen = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-            const double cu = c[0] * d.ux + c[1] * d.uy + c[2] * d.uz;
-            const double cv = c[0] * d.vx + c[1] * d.vy + c[2] * d.vz;
-            const double ca = c[0] * d.ax + c[1] * d.ay + c[2] * d.az;
-            const double l1 = std::fabs((double)(float)cu) + std::fabs((double)(float)cv) + std::fabs((double)(float)ca);
-            const double mc = 0x1p-8 * l1 * (1.0 + 0x1p-20);
-            const bool ok = l_ok && cull[i].rr >= 0x1p-50f && l1 < 0x1p38 && std::isfinite(cull[i].rr) && std::isfinite(clen);
-            if (!ok) {
-                e = DevShadowCull{0.0f, 0.0f, INFINITY, INFINITY};
-                continue;
-            }
-            e.cu = (float)cu;
-            e.cv = (float)cv;
-            e.ca = std::nextafter((float)((double)(float)ca + mc), INFINITY);
-            e.rr = std::nextafter((float)((double)cull[i].rr + 0x1p-18 * clen + mc), INFINITY);
-        }
-    }
-}
-
-// Shadow grid of one light (DevShadowGrid; culling only -- a sphere left out of a lane's mask must
-// provably not block that lane's shadow ray in binary32).  The argument (rt_kernel.hip cull_mask):
-// IntersectsSphere yields disc < 0 when the exact line-to-centre distance D >= r (1 + 3 eps) +
-// 9.2e-4 |u| (u = hp - C), and b >= 0 when (hp - C).A >= 4 eps |u|; either makes the ray unblocked.
-// For a lane with |hp|_1 <= B: |u| <= |C|_1 + B, and its binary32 projections u_f = hp.U etc. are
-// within 2^-21 |hp|_1 <= 2^-21 B of the exact ones in the double frame (U_f rounds U to 2^-24, three
-// products and two sums round to 2^-24 each).  So, with T_j = r'_j + 2^-8 (|C_j|_1 + B) + 2^-20 B
-// (r' >= r (1 + 2^-8) from DevSphereCull): a sphere whose centre lies farther than T_j from every
-// (u, v) a lane of cell (iu, iv) can have -- the cell's interval from the device's own fma/floor
-// mapping (cell_lo/cell_hi), grown by 2^-20 B -- has D > r (1 + 3 eps) + 2^-8 |u| (a 4x margin
-// over 9.2e-4); cells outside the grid hold no such disc at all.  Axially, sphere j may be ahead of
-// slab k only if ca_j + mB_j > a_lo(k), mB_j = 2^-8 (|C_j|_1 + B) + 2^-20 B; otherwise every lane in
-// the slab has (hp - C).A >= 2^-8 (|C_j|_1 + B) >> 4 eps |u| (b >= 0).  Lanes beyond B: their own
-// margin far_k |hp|_1 (far_k = 2^-8 + 2^-20, rounded up) on the box of all discs, and the slab of
-// a_f - (far_k |hp|_1 - 2^-8 B), which raises the slab rule's margin from B to |hp|_1.  Spheres
-// without a valid record (NaN/inf, r^2 < 2^-100, |C|_1 >= 2^30) are never culled (`always`); a
-// light whose |p|^2 lies outside [2^-40, 2^40] (the analysis' range) culls nothing.
-// The bundle kernel's sphere clusters (rt_internal.h DevCluster): median splits of the sphere centres along the
-// widest axis of their box until a group holds at most `size` spheres; each cluster's centre is the middle of
-// its members' box (rounded to float) and R, computed in double from that rounded centre and rounded up, bounds
-// |c_i - centre| + r'_i for every member (r' = the DevSphereCull radius, itself >= r (1 + 2^-8)).  A member
-// without a usable cull record (NaN / infinite centre or radius) makes its cluster's R NaN: never culled.
-// Returns the cluster count (<= MAX_CLUSTERS).
-int build_clusters(const DevSphereCull* cull, int S, int size, DevCluster* out) {
-    std::vector<std::vector<int>> todo(1, std::vector<int>((size_t)S)), groups;
-    for (int i = 0; i < S; ++i) todo[0][(size_t)i] = i;
-    while (!todo.empty()) {
-        std::vector<int> g = std::move(todo.back());
-        todo.pop_back();
-        if ((int)g.size() <= size) {
-            groups.push_back(std::move(g));
-            continue;
-        }
-        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int i : g) {
-            const double c[3] = {cull[i].cx, cull[i].cy, cull[i].cz};
-            for (int k = 0; k < 3; ++k) lo[k] = std::fmin(lo[k], c[k]), hi[k] = std::fmax(hi[k], c[k]);
-        }
-        int ax = 0;
-        for (int k = 1; k < 3; ++k)
-            if (hi[k] - lo[k] > hi[ax] - lo[ax]) ax = k;
-        auto key = [&](int i) {  // (NaN last: a strict weak order for the sort)
-            const float k = ax == 0 ? cull[i].cx : ax == 1 ? cull[i].cy : cull[i].cz;
-            return std::isnan(k) ? INFINITY : k;
-        };
-        std::stable_sort(g.begin(), g.end(), [&](int a, int b) { return key(a) < key(b); });
-        const size_t h = g.size() / 2;
-        todo.emplace_back(g.begin(), g.begin() + (long)h);
-        todo.emplace_back(g.begin() + (long)h, g.end());
-    }
-    if ((int)groups.size() > MAX_CLUSTERS) return 0;
-    int n = 0;
-    for (const std::vector<int>& g : groups) {
-        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        bool usable = true;
-        unsigned long long m = 0;
-        for (int i : g) {
-            const double c[3] = {cull[i].cx, cull[i].cy, cull[i].cz};
-            for (int k = 0; k < 3; ++k) lo[k] = std::fmin(lo[k], c[k]), hi[k] = std::fmax(hi[k], c[k]);
-            usable = usable && std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]) &&
-                     std::isfinite((double)cull[i].rr) && cull[i].rr >= 0x1p-50f;
-            m |= 1ull << i;
-        }
-        DevCluster& c = out[n++];
-        c.cx = (float)((lo[0] + hi[0]) / 2), c.cy = (float)((lo[1] + hi[1]) / 2), c.cz = (float)((lo[2] + hi[2]) / 2);
-        double R = 0;
-        for (int i : g) {
-            const double dx = (double)cull[i].cx - c.cx, dy = (double)cull[i].cy - c.cy, dz = (double)cull[i].cz - c.cz;
-            R = std::fmax(R, std::sqrt(dx * dx + dy * dy + dz * dz) + (double)cull[i].rr);
-        }
-        c.R = usable && R < 0x1p40 ? std::nextafter((float)(R * (1.0 + 0x1p-20)), INFINITY) : NAN;
-        c.members = m;
-        c.pad = 0;
-    }
-    return n;
-}
-
-void build_shadow_grid(const DevLight& l, const Frame3& f, const DevSphere* sph, const DevSphereCull* cull, int S,
-                       DevShadowGrid& g, unsigned long long* grid, unsigned long long* slab) {
-    std::memset(&g, 0, sizeof g);
-    std::memset(grid, 0, sizeof(unsigned long long) * SHGRID_N * SHGRID_N);
-    std::memset(slab, 0, sizeof(unsigned long long) * (SHGRID_SLABS + 2));
-    const unsigned long long all = S >= 64 ? ~0ull : ((1ull << S) - 1ull);
-    g.bu0 = g.bv0 = INFINITY, g.bu1 = g.bv1 = -INFINITY;  // empty box: every far lane outside
-    const bool light_ok = l.a >= 0x1p-40f && l.a <= 0x1p40f && l.a2 < INFINITY;
-    std::vector<double> cu(S), cv(S), ca(S), c1(S), rr(S);
-    std::vector<bool> ok(S);
-    double cmax1 = 0.0;
-    for (int j = 0; j < S; ++j) {
-        const double c[3] = {sph[j].cx, sph[j].cy, sph[j].cz};
-        c1[j] = std::fabs(c[0]) + std::fabs(c[1]) + std::fabs(c[2]);
-        rr[j] = cull[j].rr;
-        ok[j] = light_ok && std::isfinite(c1[j]) && c1[j] < 0x1p30 && std::isfinite(rr[j]) &&
-                (double)sph[j].r2 >= 0x1p-100 && rr[j] > 0.0;
-        if (!ok[j]) {
-            g.always |= 1ull << j;
-            continue;
-        }
-        cu[j] = c[0] * f.U[0] + c[1] * f.U[1] + c[2] * f.U[2];
-        cv[j] = c[0] * f.V[0] + c[1] * f.V[1] + c[2] * f.V[2];
-        ca[j] = c[0] * f.A[0] + c[1] * f.A[1] + c[2] * f.A[2];
-        cmax1 = std::max(cmax1, c1[j]);
-    }
-    if (g.always == all) {  // nothing to cull: no lane looks anything up that matters
-        g.bound = -1.0f;    // every lane "far"
-        g.far_k = 0.0f;
-        return;
-    }
-    const double B = std::min(std::max(8.0, 1.5 * cmax1), 0x1p30);
-    g.bound = down(B);
-    g.far_k = up(0x1p-8 + 0x1p-20);
-    g.far_b = down(0x1p-8 * B);
-    double ulo = INFINITY, uhi = -INFINITY, vlo = INFINITY, vhi = -INFINITY, alo = INFINITY, ahi = -INFINITY;
-    double bu0 = INFINITY, bu1 = -INFINITY, bv0 = INFINITY, bv1 = -INFINITY;
-    std::vector<double> T(S), mB(S);
-    for (int j = 0; j < S; ++j) {
-        if (!ok[j]) continue;
-        T[j] = rr[j] + 0x1p-8 * (c1[j] + B) + 0x1p-20 * B;
-        mB[j] = 0x1p-8 * (c1[j] + B) + 0x1p-20 * B;
-        ulo = std::min(ulo, cu[j] - T[j]), uhi = std::max(uhi, cu[j] + T[j]);
-        vlo = std::min(vlo, cv[j] - T[j]), vhi = std::max(vhi, cv[j] + T[j]);
-        alo = std::min(alo, ca[j] + mB[j]), ahi = std::max(ahi, ca[j] + mB[j]);
-        const double t0 = rr[j] + 0x1p-8 * c1[j];  // far lanes add their own |hp| term
-        bu0 = std::min(bu0, cu[j] - t0), bu1 = std::max(bu1, cu[j] + t0);
-        bv0 = std::min(bv0, cv[j] - t0), bv1 = std::max(bv1, cv[j] + t0);
-    }
-    g.bu0 = down(bu0), g.bu1 = up(bu1), g.bv0 = down(bv0), g.bv1 = up(bv1);
-    // grid over [lo, hi] padded by half a cell (lanes mapped outside it see no disc: checked below)
-    auto axis = [](double lo, double hi, int n, float& s, float& o) {
-        const double cs = (hi - lo) / (n - 1);  // n - 1 cells span the range, half a cell of pad each side
-        const double lo2 = lo - 0.5 * cs;
-        s = (float)(1.0 / cs);
-        o = (float)(-lo2 * (double)s);
-    };
-    axis(ulo, uhi, SHGRID_N, g.su, g.ou);
-    axis(vlo, vhi, SHGRID_N, g.sv, g.ov);
-    bool sound = g.su > 0.0f && g.sv > 0.0f && std::isfinite(g.su) && std::isfinite(g.sv) && std::isfinite(g.ou) &&
-                 std::isfinite(g.ov);
-    // a lane mapped below cell 0 / above cell N-1 lies outside every disc
-    sound = sound && cell_hi(-1, g.su, g.ou) + 0x1p-20 * B < ulo && cell_lo(SHGRID_N, g.su, g.ou) - 0x1p-20 * B > uhi &&
-            cell_hi(-1, g.sv, g.ov) + 0x1p-20 * B < vlo && cell_lo(SHGRID_N, g.sv, g.ov) - 0x1p-20 * B > vhi;
-    if (sound) {
-        for (int iv = 0; iv < SHGRID_N; ++iv) {
-            const double v0 = cell_lo(iv, g.sv, g.ov) - 0x1p-20 * B, v1 = cell_hi(iv, g.sv, g.ov) + 0x1p-20 * B;
-            for (int iu = 0; iu < SHGRID_N; ++iu) {
-                const double u0 = cell_lo(iu, g.su, g.ou) - 0x1p-20 * B, u1 = cell_hi(iu, g.su, g.ou) + 0x1p-20 * B;
-                unsigned long long m = 0;
-                for (int j = 0; j < S; ++j) {
-                    if (!ok[j]) continue;
-                    const double du = std::max(0.0, std::max(u0 - cu[j], cu[j] - u1));
-                    const double dv = std::max(0.0, std::max(v0 - cv[j], cv[j] - v1));
-                    if (du * du + dv * dv <= T[j] * T[j] * (1.0 + 0x1p-30)) m |= 1ull << j;
-                }
-                grid[iv * SHGRID_N + iu] = m;
-            }
-        }
-    } else {  // (degenerate extents) every lane takes every sphere through the far path
-        g.bound = -1.0f;
-        g.bu0 = -INFINITY, g.bu1 = INFINITY, g.bv0 = -INFINITY, g.bv1 = INFINITY;
-    }
-    // axial slabs over [alo, ahi]: entry k + 1 for slab k (-1: below the range, every sphere)
-    {
-        const double cs = std::max((ahi - alo) / SHGRID_SLABS, 1e-30);
-        g.sa = (float)(1.0 / cs);
-        g.oa = (float)(-alo * (double)g.sa);
-        const bool sa_ok = g.sa > 0.0f && std::isfinite(g.sa) && std::isfinite(g.oa);
-        slab[0] = all;
-        for (int k = 0; k <= SHGRID_SLABS; ++k) {
-            const double a_lo = sa_ok ? cell_lo(k, g.sa, g.oa) : -INFINITY;
-            unsigned long long m = 0;
-            for (int j = 0; j < S; ++j)
-                if (ok[j] && ca[j] + mB[j] > a_lo) m |= 1ull << j;
-            slab[k + 1] = m;
-        }
-        if (!sa_ok) g.sa = 0.0f, g.oa = 0.0f;  // every lane in slab 0 (= every valid sphere)
-    }
-}
-}  // namespace
-
 int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_plane* planes, int n_planes,
                  const rt_light* lights, int n_lights, rt_vec3 ambient, int recursion_limit) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "NULL context");
@@ -1703,135 +1028,20 @@ int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_
         return fail(ctx, RT_ERR_UNSUPPORTED, "recursion_limit %d > RT_MAX_RECURSION_LIMIT (%d)", recursion_limit,
                     RT_MAX_RECURSION_LIMIT);
 
-    SceneLayout L;
-    L.S = n_spheres, L.P = n_planes, L.L = n_lights, L.limit = recursion_limit;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    // the sphere table is padded to an even count (the direct kernel's loops take spheres in
-    // pairs) with a sphere that never hits: NaN centre and radius^2 make every comparison of
-    // IntersectsSphere false (no candidate, t = 0, no shadow)
-    const int s_pad = n_spheres + (n_spheres & 1);
-    L.off_sph = 0;
-    L.off_mat = al(L.off_sph + sizeof(DevSphere) * (size_t)s_pad);
-    L.off_pl = al(L.off_mat + sizeof(DevMaterial) * (size_t)(n_spheres + n_planes));
-    L.off_li = al(L.off_pl + sizeof(DevPlane) * (size_t)n_planes);
-    L.off_cull = al(L.off_li + sizeof(DevLight) * (size_t)n_lights);
-    L.off_shcull = al(L.off_cull + sizeof(DevSphereCull) * (size_t)n_spheres);
-    L.has_shcull = (long long)n_lights * (long long)n_spheres <= SHADOW_CULL_MAX_ENTRIES;
-    // shadow grids: the bundle kernel's merged pass only (merged_class 1 or 2, whatever the lights' 2a);
-    // RT_SHADOW_GRID=0 keeps the per-level bound (A/B and fallback tests)
-    const char* gv = std::getenv("RT_SHADOW_GRID");
-    L.has_shg = merged_class(n_spheres, n_lights, true) != 0 && !(gv && std::strcmp(gv, "0") == 0);
-    L.off_shg = al(L.off_shcull + (L.has_shcull ? sizeof(DevShadowCull) * (size_t)n_lights * (size_t)n_spheres : 0));
-    L.off_shgrid = al(L.off_shg + (L.has_shg ? sizeof(DevShadowGrid) * (size_t)n_lights : 0));
-    L.off_shslab = al(L.off_shgrid + (L.has_shg ? sizeof(unsigned long long) * SHGRID_N * SHGRID_N * (size_t)n_lights : 0));
-    L.off_clus = al(L.off_shslab + (L.has_shg ? sizeof(unsigned long long) * (SHGRID_SLABS + 2) * (size_t)n_lights : 0));
-    // per-lane cluster pre-cull of the bundle kernel's trace bundles (CULL_MIN_SPHERES <= S <= 64);
-    // RT_TRACE_CLUSTERS=0 turns it off, =2..16 sets the cluster size (A/B)
-    int csize = CLUSTER_SIZE;
-    if (const char* cv = std::getenv("RT_TRACE_CLUSTERS")) csize = std::atoi(cv);
-    const bool want_clus = n_spheres >= CULL_MIN_SPHERES && n_spheres <= 64 && csize >= 1;
-    L.off_shpre = al(L.off_clus + (want_clus ? sizeof(DevCluster) * MAX_CLUSTERS : 0));
-    // the direct kernel's shadow pre-test (S < CULL_MIN_SPHERES); RT_SHADOW_PRE=0 turns it off (A/B)
-    const char* pv = std::getenv("RT_SHADOW_PRE");
-    L.has_shpre = n_spheres < CULL_MIN_SPHERES && n_lights >= 1 && !(pv && std::strcmp(pv, "0") == 0);
-    // the direct kernel's mirrored screen boxes, built per view (view_mirror_boxes); RT_MIRROR_BOX=0 turns them off (A/B)
-    const char* mv = std::getenv("RT_MIRROR_BOX");
-    L.mirror_box = !(mv && std::strcmp(mv, "0") == 0);
-    L.bytes = al(L.off_shpre + (L.has_shpre ? sizeof(DevShadowCull) * (size_t)n_lights * (size_t)s_pad : 0)) + 256;
-
-    std::vector<unsigned char> blob(L.bytes, 0);
-    DevSphere* sph = (DevSphere*)(blob.data() + L.off_sph);
-    DevMaterial* mat = (DevMaterial*)(blob.data() + L.off_mat);
-    DevPlane* pl = (DevPlane*)(blob.data() + L.off_pl);
-    DevLight* li = (DevLight*)(blob.data() + L.off_li);
-    DevSphereCull* cull = (DevSphereCull*)(blob.data() + L.off_cull);
-    for (int i = 0; i < n_spheres; ++i) {
-        const rt_sphere& s = spheres[i];
-        sph[i] = DevSphere{s.center.x, s.center.y, s.center.z, s.radius * s.radius};  // :336
-        mat[i] = dev_material(s.material, ambient);
-        // cull radius: an upper bound of sqrt(r^2) (1 + 2^-8), rounded up (NaN stays NaN)
-        const double rr = std::sqrt((double)sph[i].r2) * (1.0 + 0x1p-8);
-        cull[i] = DevSphereCull{sph[i].cx, sph[i].cy, sph[i].cz, std::nextafter((float)rr, INFINITY)};
-    }
-    for (int i = n_spheres; i < s_pad; ++i) sph[i] = DevSphere{NAN, NAN, NAN, NAN};
-    L.host_sph.assign(sph, sph + n_spheres);
-    for (int i = 0; i < n_planes; ++i) {
-        const rt_plane& p = planes[i];
-        const H3 n = h3(p.normal);
-        DevPlane d;
-        std::memset(&d, 0, sizeof d);
-        d.cx = p.center.x, d.cy = p.center.y, d.cz = p.center.z;
-        d.cn = hdot(h3(p.center), n);  // Vector3.Dot(plane.center, plane.normal), :594
-        d.nx = n.x, d.ny = n.y, d.nz = n.z;
-        H3 e1 = hnormalize(hcross(n, H3{1.0f, 0.0f, 0.0f}));  // :760-763
-        if (e1.x == 0 && e1.y == 0 && e1.z == 0) e1 = hnormalize(hcross(n, H3{0.0f, 0.0f, 1.0f}));
-        H3 e2 = hnormalize(hcross(n, e1));  // :765
-        d.e1x = e1.x, d.e1y = e1.y, d.e1z = e1.z;
-        d.e2x = e2.x, d.e2y = e2.y, d.e2z = e2.z;
-        pl[i] = d;
-        mat[n_spheres + i] = dev_material(p.material, ambient);
-    }
-    L.host_pl.assign(pl, pl + n_planes);
-    std::vector<Frame3> frames((size_t)n_lights);
-    for (int i = 0; i < n_lights; ++i) {
-        const rt_light& l = lights[i];
-        const H3 p = h3(l.position);
-        DevLight d;
-        std::memset(&d, 0, sizeof d);
-        d.px = p.x, d.py = p.y, d.pz = p.z, d.intensity = l.intensity;
-        d.a = hdot(p, p);  // IntersectsSphere's a = Dot(direction, direction), :617
-        d.a2 = 2.0f * d.a;
-        d.a4 = 4.0f * d.a;
-        d.sh_t = shadow_threshold(d.a2);  // used only when a2 is finite and > 0 (wave-uniform per light)
-        if (!(d.a2 > 0.0f && d.a2 < INFINITY)) L.lights_a2_ok = false;
-        // shadow-cull frame (kernel uses it only when a is in [2^-40, 2^40])
-        const double len = std::sqrt((double)p.x * p.x + (double)p.y * p.y + (double)p.z * p.z);
-        double A[3] = {0.0, 0.0, 1.0};
-        if (len > 0 && std::isfinite(len)) A[0] = p.x / len, A[1] = p.y / len, A[2] = p.z / len;
-        const double h[3] = {std::fabs(A[0]) < 0.9 ? 1.0 : 0.0, std::fabs(A[0]) < 0.9 ? 0.0 : 1.0, 0.0};
-        double U[3] = {A[1] * h[2] - A[2] * h[1], A[2] * h[0] - A[0] * h[2], A[0] * h[1] - A[1] * h[0]};
-        const double ul = std::sqrt(U[0] * U[0] + U[1] * U[1] + U[2] * U[2]);
-        for (double& c : U) c /= ul;
-        const double V[3] = {A[1] * U[2] - A[2] * U[1], A[2] * U[0] - A[0] * U[2], A[0] * U[1] - A[1] * U[0]};
-        d.ax = (float)A[0], d.ay = (float)A[1], d.az = (float)A[2];
-        d.ux = (float)U[0], d.uy = (float)U[1], d.uz = (float)U[2];
-        d.vx = (float)V[0], d.vy = (float)V[1], d.vz = (float)V[2];
-        li[i] = d;
-        for (int k = 0; k < 3; ++k) frames[(size_t)i].U[k] = U[k], frames[(size_t)i].V[k] = V[k], frames[(size_t)i].A[k] = A[k];
-    }
-    // the dark-tile skip (rt_dark.h): planes whose material and the scene's lights pass the host part of its guard;
-    // RT_DARK_SKIP=0 leaves the bit clear (A/B)
-    const char* dv = std::getenv("RT_DARK_SKIP");
-    // the plane footprints of a view (rt_foot.h, built per view by view_fill); RT_PRIM_FOOT=0 turns them off (A/B)
-    const char* fv = std::getenv("RT_PRIM_FOOT");
-    L.prim_foot = !(fv && std::strcmp(fv, "0") == 0);
-    if (!(dv && std::strcmp(dv, "0") == 0))
-        for (int i = 0; i < n_planes; ++i)
-            if (plane_dark_ok(pl[i], mat[n_spheres + i], li, n_lights)) mat[n_spheres + i].flags |= MAT_DARK_OK;
-    if (L.has_shg)
-        for (int j = 0; j < n_lights; ++j)
-            build_shadow_grid(li[j], frames[(size_t)j], sph, cull, n_spheres, ((DevShadowGrid*)(blob.data() + L.off_shg))[j],
-                              (unsigned long long*)(blob.data() + L.off_shgrid) + (size_t)j * SHGRID_N * SHGRID_N,
-                              (unsigned long long*)(blob.data() + L.off_shslab) + (size_t)j * (SHGRID_SLABS + 2));
-    if (want_clus) L.n_clus = build_clusters(cull, n_spheres, csize, (DevCluster*)(blob.data() + L.off_clus));
-    if (L.has_shcull) {  // sphere centres in each light's shadow-cull frame (culling only)
-        DevShadowCull* sc = (DevShadowCull*)(blob.data() + L.off_shcull);
-        for (int j = 0; j < n_lights; ++j)
-            for (int i = 0; i < n_spheres; ++i) {
-                const DevLight& d = li[j];
-                const double c[3] = {cull[i].cx, cull[i].cy, cull[i].cz};
-                const double clen = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-                DevShadowCull& e = sc[(size_t)j * (size_t)n_spheres + (size_t)i];
-                e.cu = (float)(c[0] * d.ux + c[1] * d.uy + c[2] * d.uz);
-                e.cv = (float)(c[0] * d.vx + c[1] * d.vy + c[2] * d.vz);
-                e.ca = (float)(c[0] * d.ax + c[1] * d.ay + c[2] * d.az);
-                // r' + 2^-18 |C|, rounded up (NaN / inf stay: the kernel keeps such spheres)
-                e.rr = std::nextafter((float)((double)cull[i].rr + 0x1p-18 * clen), INFINITY);
-            }
-    }
-    if (L.has_shpre) build_shadow_pre(li, n_lights, cull, n_spheres, s_pad, (DevShadowCull*)(blob.data() + L.off_shpre));
-    for (int i = 0; i < n_spheres + n_planes; ++i)
-        if ((mat[i].flags & MAT_SPEC) && mat[i].pow_kind == POW_GENERIC) L.generic_pow = true;
+    // the switches of rt_scene.h SceneOptions (A/B and fallback tests): RT_<NAME>=0 turns a table off,
+    // RT_TRACE_CLUSTERS=0 the clusters, =2..16 sets the cluster size
+    auto off = [](const char* name) {
+        const char* v = std::getenv(name);
+        return v && std::strcmp(v, "0") == 0;
+    };
+    SceneOptions opt;
+    opt.shadow_grid = !off("RT_SHADOW_GRID");
+    if (const char* cv = std::getenv("RT_TRACE_CLUSTERS")) opt.cluster_size = std::atoi(cv);
+    opt.shadow_pre = !off("RT_SHADOW_PRE");
+    opt.mirror_box = !off("RT_MIRROR_BOX");
+    opt.dark_skip = !off("RT_DARK_SKIP");
+    opt.prim_foot = !off("RT_PRIM_FOOT");
+    SceneLayout L = scene_build(spheres, n_spheres, planes, n_planes, lights, n_lights, ambient, recursion_limit, opt);
     for (Device& d : ctx->dev) {
         DeviceGuard guard(d.id);
         // frames in flight on any stream (rt_render_device callers', the async slots) read
@@ -1839,9 +1049,8 @@ int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_
         HIP_TRY(ctx, hipDeviceSynchronize());
         int rc = grow(ctx, &d.d_scene, &d.scene_cap, L.bytes);
         if (rc != RT_OK) return rc;
-        HIP_TRY(ctx, hipMemcpy(d.d_scene, blob.data(), L.bytes, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d.d_scene, L.host_blob.data(), L.bytes, hipMemcpyHostToDevice));
     }
-    L.host_blob = std::move(blob);
     ctx->layout = std::move(L);
     ctx->has_scene = true;
     ctx->view_ok = false;
@@ -1895,29 +1104,10 @@ int rt_get_camera(const rt_ctx* ctx, rt_camera* camera) {
     return RT_OK;
 }
 
-// CameraForwardDirection / CameraRightDirection / CameraUpDirection (RayTracer.cs:511-523):
-// double trig of the float yaw/pitch, each component cast to float; Up = Cross(Right, Fwd).
-// View params (Tick, :892-896): planeHeight = 0.3f * (float)Math.Tan(30f * (MathF.PI/180f)) * 2,
-// planeWidth = planeHeight * ((float)width / height).
+// The camera basis and view plane of RayTracer.cs:511-523 and :892-896 (rt_view.h camera_view).
 int rt_camera_view(const rt_camera* c, int width, int height, rt_view* out) {
     if (!c || !out || width <= 0 || height <= 0) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_camera_view: bad args");
-    const double p = (double)c->pitch, y = (double)c->yaw;
-    const H3 f{(float)(std::cos(p) * std::sin(y)), (float)-std::sin(p), (float)(std::cos(p) * std::cos(y))};
-    const H3 r{(float)std::cos(y), 0.0f, (float)-std::sin(y)};
-    const H3 u = hcross(r, f);
-    out->position = c->position;
-    out->right = rt_vec3{r.x, r.y, r.z};
-    out->up = rt_vec3{u.x, u.y, u.z};
-    out->forward = rt_vec3{f.x, f.y, f.z};
-    const float near_clip = 0.3f, fov = 60.0f;
-    const float deg2rad = (float)M_PI / 180.0f;  // MathHelper.DegreesToRadians: d * (MathF.PI / 180f)
-    const float rad = (fov * 0.5f) * deg2rad;
-    const float plane_height = near_clip * (float)std::tan((double)rad) * 2;
-    const float aspect = (float)width / (float)height;
-    out->plane_width = plane_height * aspect;
-    out->plane_height = plane_height;
-    out->near_clip = near_clip;
-    return RT_OK;
+    return camera_view(*c, width, height, out);
 }
 
 // OnKeyPress, RayTracer.cs:543-554: position +/- direction * (0.05, 0.05, 0.05).
