@@ -238,6 +238,40 @@ int rt_get_supersampling(const rt_ctx* ctx, int* out_k);
  * Returns RT_ERR_INVALID_ARG for a NULL ctx (or out_threshold) or a threshold outside 0..256. */
 int rt_set_adaptive_sampling(rt_ctx* ctx, int threshold);
 int rt_get_adaptive_sampling(const rt_ctx* ctx, int* out_threshold);
+/* (ABI 10 addition) Progressive anti-aliasing for a display loop: k = 1 (the default, off), 2, 4 or 8.  While the
+ * camera rests, each Tick call -- rt_render, rt_render_async, rt_render_device, and only these -- traces one more
+ * sample per pixel and shows the mean so far; when anything of the view changes, the image is the plain frame again.
+ * Sample order: with s = log2 k, sample n of 0 .. k*k - 1 is found from n's base-4 digits d_0 (least significant)
+ * .. d_{s-1}: digit d_t gives bit s - 1 - t of the sample's column i from its bit 0, and bit s - 1 - t of its row j
+ * from its bit 1.  k = 4: (i, j) = (0,0) (2,0) (0,2) (2,2) (1,0) (3,0) (1,2) (3,2) (0,1) (2,1) (0,3) (2,3) (1,1)
+ * (3,1) (1,3) (3,3).  Sample (i, j) of output pixel (x, y) is the reference's pixel (k x + i, k y + j) of the
+ * k width x k height frame, exactly as for rt_set_supersampling.
+ * Output: P_c is, per 8-bit channel after ShiftColor, (sum of samples 0 .. c-1 + c/2) / c in integer arithmetic
+ * (c/2 floors).  P_1 is the plain frame bit for bit, P_{k*k} is rt_set_supersampling(k)'s frame, and P_{4^t} is the
+ * frame of rt_set_supersampling(2^t): the coarse sub-grids come first.
+ * View key: the scene (any rt_set_scene makes a new one), the camera's five floats compared as bits, width, height
+ * and the view height, k, and the number of band workers (a worker's accumulator follows its packed band set, which
+ * no chunking changes).  The n-th consecutive Tick call whose key equals the previous Tick's outputs
+ * P_min(n, k*k); any other Tick outputs P_1 and starts a new run.  rt_set_camera with unchanged values does not
+ * restart; rt_reset_progressive forces a restart; a Tick that fails ends the run.  rt_render_async captures the
+ * Tick's place in the run when it is queued, as it captures the camera.
+ * rt_get_progressive returns the factor and the c of the last issued Tick frame (0 before any; 1 while k = 1).
+ * Cost: a Tick that outputs P_1 runs exactly the launch the library runs without this call (a moving camera pays a
+ * key compare on the host); the Tick for P_2 traces samples 0 and 1 in one launch and starts the accumulator
+ * without reading it; the Ticks for P_3 .. P_{k*k} trace one sample per pixel; later Ticks trace nothing and emit
+ * P_{k*k} from the accumulator.  Memory: 8 bytes per pixel of each worker's share, allocated at the first P_2 Tick,
+ * freed by rt_set_progressive(ctx, 1) and rt_destroy.
+ * Limits: while k > 1 a Tick with rt_set_supersampling also above 1 returns RT_ERR_UNSUPPORTED, and
+ * (long long) k width * k height (the view height, when set) above 2^31 - 1 returns RT_ERR_INVALID_ARG.  The band,
+ * batch, path, shutter and tile renders, rt_count_work and rt_debug_segments ignore the setting and do not disturb
+ * a run.  Contexts of any n_gpus and flags: each worker accumulates its own share.
+ * Statistics: frames and pixels count every Tick, launches the launches issued (a converged Tick's emit is one);
+ * with counting on, primary_rays grows by the samples traced -- width * height, then twice that, then width *
+ * height per Tick, then 0 -- and reflect_rays / shadow_rays by those samples' rays.
+ * Returns RT_ERR_INVALID_ARG for a NULL ctx, a NULL out pointer or any other k. */
+int rt_set_progressive(rt_ctx* ctx, int k);
+int rt_get_progressive(const rt_ctx* ctx, int* out_k, int* out_samples);
+int rt_reset_progressive(rt_ctx* ctx);
 int rt_get_camera(const rt_ctx* ctx, rt_camera* camera);
 int rt_camera_view(const rt_camera* camera, int width, int height, rt_view* out_view);
 int rt_camera_on_key(rt_camera* camera, int key);

@@ -49,6 +49,9 @@ internal static class Native {
     [DllImport(Lib)] internal static extern int rt_set_supersampling(IntPtr ctx, int k);  // ABI 10 addition
     [DllImport(Lib)] internal static extern int rt_set_adaptive_sampling(IntPtr ctx, int threshold);  // ABI 10 addition
     [DllImport(Lib)] internal static extern int rt_get_adaptive_sampling(IntPtr ctx, out int threshold);
+    [DllImport(Lib)] internal static extern int rt_set_progressive(IntPtr ctx, int k);  // ABI 10 addition
+    [DllImport(Lib)] internal static extern int rt_get_progressive(IntPtr ctx, out int k, out int samples);
+    [DllImport(Lib)] internal static extern int rt_reset_progressive(IntPtr ctx);
 
     internal static void Check(int rc, IntPtr ctx) {
         if (rc != 0) throw new InvalidOperationException($"libraytracer_hip error {rc}: {Marshal.PtrToStringAnsi(rt_last_error(ctx))}");
@@ -79,6 +82,10 @@ internal sealed class RayTracer : IDisposable {
         // a channel are supersampled; 0 or unset: every pixel
         int adaptive = int.TryParse(Environment.GetEnvironmentVariable("RT_ADAPTIVE"), out int t) ? t : 0;
         Native.Check(Native.rt_set_adaptive_sampling(_ctx, adaptive), _ctx);
+        // RT_PROGRESSIVE=2|4|8 (with RT_SAMPLES unset): while the camera rests every Tick adds one sample per pixel of
+        // the k x k block and shows the mean so far; a Tick after the camera moved is the plain frame again
+        int progressive = int.TryParse(Environment.GetEnvironmentVariable("RT_PROGRESSIVE"), out int pk) ? pk : 1;
+        Native.Check(Native.rt_set_progressive(_ctx, progressive), _ctx);
         // the hard-coded scene of RayTracer.cs:441-469
         static Native.Vec3 V(float x, float y, float z) => new(x, y, z);
         static Native.Material M(Native.Vec3 kd, Native.Vec3 ka, Native.Vec3 ks, float n, Native.Vec3 km) =>

@@ -25,6 +25,7 @@
 #include "../../include/raytracer_hip.h"
 #include "rt_bands.h"
 #include "rt_internal.h"
+#include "rt_progressive.h"
 #include "rt_scene.h"
 #include "rt_view.h"
 
@@ -160,7 +161,8 @@ struct Device {
                                               // frame f's copy done -> EV_RING + f % RING
         EV_PATH_TRACED = EV_RING + RING,      // [2] rt_render_path: d_path[b] traced,
         EV_PATH_COPIED = EV_PATH_TRACED + 2,  // [2] copied
-        EV_COUNT = EV_PATH_COPIED + 2
+        EV_PROG = EV_PATH_COPIED + 2,         // the last launch that touched the progressive accumulator (d_prog)
+        EV_COUNT = EV_PROG + 1
     };
     hipEvent_t ev[EV_COUNT] = {};
     uint64_t frames_issued = 0;
@@ -182,6 +184,14 @@ struct Device {
     // (copy_stream) under the trace of chunk c + 1
     int32_t* d_path[2] = {nullptr, nullptr};
     size_t path_cap[2] = {0, 0};
+    // rt_set_progressive: this worker's accumulator, one ResolveSum per pixel of its packed band set (bands g, g + n,
+    // ... of TICK_BAND_ROWS rows; one worker: the frame), made at the first Tick that accumulates.  Only PROG trace
+    // launches touch it, in issue order: a Tick on another stream than the last one's (rt_render_device on the
+    // caller's, rt_render_async on the async stream) first waits for EV_PROG.
+    ResolveSum* d_prog = nullptr;
+    size_t prog_cap = 0;
+    hipStream_t prog_stream = nullptr;
+    bool prog_touched = false;
     float* d_view_tab = nullptr;  // lx[W] then ly[H] (view_tables)
     size_t view_tab_cap = 0;
     int tab_w = -1, tab_h = -1;
@@ -267,6 +277,13 @@ struct rt_ctx {
     int view_height = 0;  // rt_set_view_height: the view's height (0: each render's own frame height)
     int ss_log2 = 0;      // rt_set_supersampling: log2 of the factor k (0: off)
     int adapt_thr = 0;    // rt_set_adaptive_sampling: the threshold T in 1..256 (0: off); in effect while ss_log2 > 0
+    // rt_set_progressive (rt_progressive.h): log2 of the factor (0: off), the run so far, the c of the last issued
+    // Tick frame, and -- only while a Tick call issues its launches -- that Tick's plan (PROG_PLAIN otherwise: band,
+    // batch and path renders never see one)
+    int prog_log2 = 0;
+    ProgRun prog_run;
+    int prog_last = 0;
+    ProgPlan tick_plan{PROG_PLAIN, 0, 1, 1};
     LaunchParams view_lp{};
 };
 
@@ -604,10 +621,11 @@ int launch_counted(rt_ctx* ctx, Device& d, hipStream_t stream, const LaunchParam
     if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString((hipError_t)e));
     ctx->launches++;
     if (lp.adapt_thr > 0) ss = 0;
+    // (a progressive launch: the samples it traces per pixel, none when it only emits)
+    const uint64_t per_pixel = lp.prog_acc != nullptr ? (uint64_t)lp.prog_n : (uint64_t)1 << (2 * ss);
     for (int k = 0; k < nb && ctx->counting; ++k) {
         const long long y0 = (long long)(first + k * step) * band_rows;
-        ctx->prim_rays += ((uint64_t)std::min<long long>(band_rows, (long long)H - y0) * (uint64_t)W * (uint64_t)n_frames)
-                          << (2 * ss);
+        ctx->prim_rays += (uint64_t)std::min<long long>(band_rows, (long long)H - y0) * (uint64_t)W * (uint64_t)n_frames * per_pixel;
     }
     return RT_OK;
 }
@@ -634,6 +652,9 @@ struct TraceReq {
     const EncTarget* enc = nullptr;   // the fused tile encoder's target
     const CopyJob* slice = nullptr;   // a Tick hand-off that rides in the launch as its copy slice
     int max_bands = INT_MAX;
+    // a Tick of a progressive run (rt_ctx::tick_plan is PROG_TRACE or PROG_EMIT): the worker's accumulator at the
+    // request's first band, packed like a band set; nullptr: any other launch
+    ResolveSum* acc = nullptr;
 };
 
 // Launch the trace `q` on device d.
@@ -644,10 +665,15 @@ struct TraceReq {
 int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, const TraceReq& q) {
     const int W = q.W, H = q.H, band_rows = q.band_rows, first = q.first, step = q.step, n_frames = q.n_frames;
     const EncTarget* enc = q.enc;
-    const int ss = ctx->ss_log2;
+    // A progressive Tick beyond its first frame (q.acc): a launch on the k W x k H sample frame like a supersampling
+    // one, with the run's factor (rt_set_supersampling is off: TickScope::begin refused the Tick otherwise).
+    const bool prog = q.acc != nullptr;
+    const int ss = prog ? ctx->prog_log2 : ctx->ss_log2;
     if (ss > 0 && enc) return fail(ctx, RT_ERR_UNSUPPORTED, "the fused tile encoder does not supersample");
-    const int thr = ss > 0 ? ctx->adapt_thr : 0;
+    const int thr = ss > 0 && !prog ? ctx->adapt_thr : 0;
     RT_TRY(check_adaptive_bands(ctx, band_rows, H));
+    if (prog && (ss <= 0 || ctx->tick_plan.kind == PROG_PLAIN || enc || n_frames != 1 || !adaptive_band_ok(band_rows, H)))
+        return fail(ctx, RT_ERR_UNSUPPORTED, "progressive launch outside a Tick's band plan (band_rows %d, height %d)", band_rows, H);
     LaunchParams lp;
     std::memset(&lp, 0, sizeof lp);
     RT_TRY(view_params(ctx, W << ss, H << ss, lp, ss));
@@ -661,6 +687,12 @@ int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, const TraceReq& q) {
         lp.local_rows = nb * lp.band_rows;
         lp.ss_log2 = ss;
         lp.adapt_thr = thr;
+        if (prog) {
+            const ProgPlan& pl = ctx->tick_plan;
+            lp.prog_acc = q.acc;
+            lp.prog_first = pl.first, lp.prog_n = pl.samples;
+            for (int i = 0; i < pl.samples; ++i) lp.prog_pass[i] = prog_pass(ss, pl.first + i);
+        }
     } else {
         lp.band_rows = band_rows;
         lp.local_rows = nb * band_rows;
@@ -705,8 +737,16 @@ int trace_bands(rt_ctx* ctx, Device& d, hipStream_t stream, const TraceReq& q) {
         lp.out_frame_bytes = 0;
     }
     probe = probe && order_begin(d, cand, stream);
+    if (prog) {  // the accumulator's launches run in issue order whatever streams the Ticks use
+        RT_TRY(ensure_event(ctx, &d.ev[Device::EV_PROG]));
+        if (d.prog_touched && d.prog_stream != stream) HIP_TRY(ctx, hipStreamWaitEvent(stream, d.ev[Device::EV_PROG], 0));
+    }
     const int rc = launch_counted(ctx, d, stream, lp, "trace", W, H, band_rows, first, step, nb, n_frames, ss);
     if (probe) order_end(d, stream);
+    if (prog && rc == RT_OK) {
+        HIP_TRY(ctx, hipEventRecord(d.ev[Device::EV_PROG], stream));
+        d.prog_stream = stream, d.prog_touched = true;
+    }
     return rc;
 }
 
@@ -747,12 +787,64 @@ int32_t* mapped_host(const rt_ctx* ctx, int g, void* host, size_t bytes) {
 }
 
 // The trace of bands [k0, k1) of a share into the packed band set at buf (band 0); `slice` rides in the launch.
-TraceReq share_req(const Share& sh, int W, int H, int k0, int k1, int32_t* buf, const CopyJob* slice = nullptr) {
+// acc: the worker's progressive accumulator (band 0) in a Tick that uses it (tick_acc), offset like buf.
+TraceReq share_req(const Share& sh, int W, int H, int k0, int k1, int32_t* buf, const CopyJob* slice = nullptr,
+                   ResolveSum* acc = nullptr) {
     TraceReq q{W, H, sh.band_rows, sh.first + k0 * sh.step, sh.step, buf + (size_t)k0 * sh.band_rows * W};
     q.slice = slice;
     q.max_bands = k1 - k0;
+    q.acc = acc ? acc + (size_t)k0 * sh.band_rows * W : nullptr;
     return q;
 }
+// Worker d's accumulator in a Tick whose plan uses it, else nullptr (the plain launch).
+ResolveSum* tick_acc(const rt_ctx* ctx, const Device& d) { return ctx->tick_plan.kind != PROG_PLAIN ? d.d_prog : nullptr; }
+// A Tick call (rt_render, rt_render_async, rt_render_device) under rt_set_progressive: begin() compares the view key
+// with the last Tick's, advances the run and leaves the Tick's plan in ctx->tick_plan for the launches the call
+// issues -- captured at enqueue time, like the camera; the scope's end takes the plan away again, so that no other
+// render sees one, and a Tick that failed ends the run (its accumulator may be half written: the next Tick is P_1).
+// With the feature off begin() touches nothing but the reported count.
+struct TickScope {
+    rt_ctx* ctx;
+    bool done = false;
+    explicit TickScope(rt_ctx* c) : ctx(c) {}
+    ~TickScope() {
+        if (!done) ctx->prog_run.count = 0;
+        else ctx->prog_last = ctx->tick_plan.divisor;
+        ctx->tick_plan = ProgPlan{PROG_PLAIN, 0, 1, 1};
+    }
+    int begin(int W, int H) {
+        const int s = ctx->prog_log2, k = 1 << s;
+        ctx->tick_plan = ProgPlan{PROG_PLAIN, 0, 1, 1};
+        if (s == 0) return RT_OK;
+        if (ctx->ss_log2 > 0)
+            return fail(ctx, RT_ERR_UNSUPPORTED, "progressive accumulation (factor %d) with rt_set_supersampling(%d) on", k,
+                        1 << ctx->ss_log2);
+        const int VH = ctx->view_height > 0 ? ctx->view_height : H;
+        if (((long long)W << s) * ((long long)VH << s) > (1LL << 31) - 1)
+            return fail(ctx, RT_ERR_INVALID_ARG, "frame size %dx%d at progressive factor %d exceeds 2^31 - 1 samples", W, VH, k);
+        const ProgKey key = prog_key(ctx->scene_gen, ctx->cam, W, H, ctx->view_height, k, ctx->n_gpus);
+        ProgPlan plan = prog_plan(&ctx->prog_run, key);
+        if (plan.kind != PROG_PLAIN) {
+            const int n = ctx->n_gpus;
+            for (int g = 0; g < n; ++g) {  // 8 bytes per pixel of each worker's packed band set
+                Device& d = ctx->dev[(size_t)g];
+                const size_t bytes = (size_t)bands_of(H, TICK_BAND_ROWS, g, n) * TICK_BAND_ROWS * (size_t)W * sizeof(ResolveSum);
+                if (d.prog_cap >= bytes) continue;
+                if (plan.first > 0) {  // (cannot happen: the run's second Tick sized it; never read what was not written)
+                    ctx->prog_run.count = 0;
+                    plan = prog_plan(&ctx->prog_run, key);
+                    break;
+                }
+                DeviceGuard guard(d.id);
+                RT_TRY(grow(ctx, (void**)&d.d_prog, &d.prog_cap, bytes));  // (hipFree waits for the launches that use it)
+                d.prog_touched = false;
+            }
+        }
+        ctx->tick_plan = plan;
+        return RT_OK;
+    }
+};
+
 // Issue each worker's pending rt_render_async hand-off (the last frame's D2H) on its async stream.
 int flush_hand(rt_ctx* ctx) {
     if (!ctx) return RT_OK;
@@ -805,7 +897,7 @@ int trace_and_copy_chunks(rt_ctx* ctx, Device& d, hipStream_t trace, const Share
         if (b.k1 <= b.k0) continue;
         hipEvent_t& ev = d.ev[Device::EV_CHUNK + c];
         RT_TRY(ensure_event(ctx, &ev));
-        RT_TRY(trace_bands(ctx, d, trace, share_req(sh, W, H, b.k0, b.k1, buf)));
+        RT_TRY(trace_bands(ctx, d, trace, share_req(sh, W, H, b.k0, b.k1, buf, nullptr, tick_acc(ctx, d))));
         HIP_TRY(ctx, hipEventRecord(ev, trace));
         HIP_TRY(ctx, hipStreamWaitEvent(d.copy_stream, ev, 0));
         RT_TRY(runtime_band_copy(ctx, sh, W, H, buf, host, d.copy_stream, pinned, b.k0, b.k1));
@@ -848,7 +940,9 @@ int gather_frame(rt_ctx* ctx, int width, int height, int32_t* dst) {
         DeviceGuard guard(d.id);
         rc = grow(ctx, (void**)&d.d_bands, &d.bands_cap, slot * sizeof(int32_t));
         if (rc == RT_OK && g == 0) rc = grow(ctx, (void**)&d.d_gather, &d.gather_cap, slot * n * sizeof(int32_t));
-        if (rc == RT_OK) rc = trace_bands(ctx, d, d.stream, TraceReq{width, height, band_rows, g, n, d.d_bands});
+        TraceReq q{width, height, band_rows, g, n, d.d_bands};
+        q.acc = tick_acc(ctx, d);
+        if (rc == RT_OK) rc = trace_bands(ctx, d, d.stream, q);
         if (rc != RT_OK) return rc;
     }
     std::vector<char> gtimed((size_t)n, 0);
@@ -1006,6 +1100,7 @@ void rt_destroy(rt_ctx* ctx) {
         if (d.d_counters) (void)hipFree(d.d_counters);
         if (d.d_counters_diag) (void)hipFree(d.d_counters_diag);
         if (d.d_view_tab) (void)hipFree(d.d_view_tab);
+        if (d.d_prog) (void)hipFree(d.d_prog);
         if (d.order.tiles.d_order) (void)hipFree(d.order.tiles.d_order);
         if (d.order.tiles.d_cost) (void)hipFree(d.order.tiles.d_cost);
         if (d.d_stage) (void)hipFree(d.d_stage);
@@ -1092,6 +1187,39 @@ int rt_get_adaptive_sampling(const rt_ctx* ctx, int* out_threshold) {
     return RT_OK;
 }
 
+int rt_set_progressive(rt_ctx* ctx, int k) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_set_progressive: NULL context");
+    const int s = prog_log2(k);
+    if (s < 0) return fail(ctx, RT_ERR_INVALID_ARG, "rt_set_progressive: factor %d is not 1, 2, 4 or 8", k);
+    if (s == ctx->prog_log2) return RT_OK;
+    ctx->prog_log2 = s;  // (the factor is part of the view key: the next Tick starts a run)
+    if (s == 0) {        // off: the accumulators go, once nothing in flight uses them
+        RT_TRY(flush_hand(ctx));
+        for (Device& d : ctx->dev) {
+            if (!d.d_prog) continue;
+            DeviceGuard guard(d.id);
+            HIP_TRY(ctx, hipDeviceSynchronize());
+            (void)hipFree(d.d_prog);
+            d.d_prog = nullptr, d.prog_cap = 0, d.prog_touched = false;
+        }
+        ctx->prog_run.count = 0;
+    }
+    return RT_OK;
+}
+
+int rt_get_progressive(const rt_ctx* ctx, int* out_k, int* out_samples) {
+    if (!ctx || !out_k || !out_samples) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_get_progressive: NULL argument");
+    *out_k = 1 << ctx->prog_log2;
+    *out_samples = ctx->prog_last;
+    return RT_OK;
+}
+
+int rt_reset_progressive(rt_ctx* ctx) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_reset_progressive: NULL context");
+    ctx->prog_run.count = 0;
+    return RT_OK;
+}
+
 int rt_set_camera(rt_ctx* ctx, const rt_camera* camera) {
     if (!ctx || !camera) return fail(ctx, RT_ERR_INVALID_ARG, "rt_set_camera: NULL argument");
     ctx->cam = *camera;
@@ -1145,11 +1273,15 @@ int rt_render_device(rt_ctx* ctx, int width, int height, int32_t* d_pixels, void
     int rc = check_ctx(ctx, width, height);
     if (rc != RT_OK) return rc;
     if (!d_pixels) return fail(ctx, RT_ERR_INVALID_ARG, "NULL d_pixels");
+    TickScope tick(ctx);
+    RT_TRY(tick.begin(width, height));
     Device& d0 = ctx->dev[0];
     hipStream_t s = (hipStream_t)hip_stream;  // NULL = the HIP null stream
     if (ctx->n_gpus == 1 && !ctx->rccl_gather) {
         DeviceGuard guard(d0.id);
-        rc = trace_bands(ctx, d0, s, TraceReq{width, height, height, 0, 1, d_pixels});
+        TraceReq q{width, height, height, 0, 1, d_pixels};
+        q.acc = tick_acc(ctx, d0);
+        rc = trace_bands(ctx, d0, s, q);
     } else {
         // n > 1: the workers start after the work already on the caller's stream (d_pixels may be in use)
         // and the caller's stream waits for the whole frame
@@ -1167,9 +1299,11 @@ int rt_render_device(rt_ctx* ctx, int width, int height, int32_t* d_pixels, void
             HIP_TRY(ctx, hipStreamWaitEvent(d.stream, d0.ev[Device::EV_JOIN], 0));
         }
         if (ctx->shared_device) {  // one device: every worker writes its bands straight into the frame
-            for (int g = 0; g < ctx->n_gpus && rc == RT_OK; ++g)
-                rc = trace_bands(ctx, ctx->dev[(size_t)g], ctx->dev[(size_t)g].stream,
-                                 TraceReq{width, height, TICK_BAND_ROWS, g, ctx->n_gpus, d_pixels, RT_BANDS_FRAME});
+            for (int g = 0; g < ctx->n_gpus && rc == RT_OK; ++g) {
+                TraceReq q{width, height, TICK_BAND_ROWS, g, ctx->n_gpus, d_pixels, RT_BANDS_FRAME};
+                q.acc = tick_acc(ctx, ctx->dev[(size_t)g]);
+                rc = trace_bands(ctx, ctx->dev[(size_t)g], ctx->dev[(size_t)g].stream, q);
+            }
         } else {  // the RCCL gather to device 0 over xGMI, reassembled into d_pixels on device 0's stream
             rc = gather_frame(ctx, width, height, d_pixels);
         }
@@ -1181,6 +1315,7 @@ int rt_render_device(rt_ctx* ctx, int width, int height, int32_t* d_pixels, void
         }
     }
     if (rc == RT_OK) {
+        tick.done = true;
         ctx->frames++;
         ctx->pixels += (uint64_t)width * (uint64_t)height;
     }
@@ -1563,7 +1698,7 @@ int tick_sync(rt_ctx* ctx, int W, int H, int32_t* pixels) {
             continue;
         }
         if (mode == TICK_RUNTIME || (nc == 1 && n == 1)) {  // the runtime's copy after the trace
-            RT_TRY(trace_bands(ctx, d, d.stream, share_req(sh, W, H, 0, sh.nb, d.d_bands)));
+            RT_TRY(trace_bands(ctx, d, d.stream, share_req(sh, W, H, 0, sh.nb, d.d_bands, nullptr, tick_acc(ctx, d))));
             const bool ctimed = begin_timed(ctx, d, 1);
             const int rc = runtime_band_copy(ctx, sh, W, H, d.d_bands, pixels, d.stream, mapped != nullptr, 0, sh.nb);
             end_timed(d, ctimed);
@@ -1574,7 +1709,7 @@ int tick_sync(rt_ctx* ctx, int W, int H, int32_t* pixels) {
         for (int c = 0; c < nc; ++c) {
             const Bands b = chunk_bands(sh, c, nc);
             if (b.k1 <= b.k0) continue;
-            const TraceReq q = share_req(sh, W, H, b.k0, b.k1, d.d_bands, &prev);
+            const TraceReq q = share_req(sh, W, H, b.k0, b.k1, d.d_bands, &prev, tick_acc(ctx, d));
             RT_TRY(trace_bands(ctx, d, d.stream, q));
             prev = share_job(sh, W, H, b.k0, b.k1, q.out, mapped);
         }
@@ -1597,6 +1732,8 @@ int rt_render(rt_ctx* ctx, int width, int height, int32_t* pixels) {
     RT_TRY(check_ctx(ctx, width, height));
     if (!pixels) return fail(ctx, RT_ERR_INVALID_ARG, "NULL pixels");
     RT_TRY(wait_pending_async(ctx));
+    TickScope tick(ctx);
+    RT_TRY(tick.begin(width, height));
     if (ctx->rccl_gather) {  // bands gathered to device 0 over RCCL, then the whole frame over its link
         Device& d0 = ctx->dev[0];
         const size_t frame_bytes = (size_t)width * height * sizeof(int32_t);
@@ -1613,6 +1750,7 @@ int rt_render(rt_ctx* ctx, int width, int height, int32_t* pixels) {
     } else {
         RT_TRY(tick_sync(ctx, width, height, pixels));
     }
+    tick.done = true;
     ctx->frames++;
     ctx->pixels += (uint64_t)width * (uint64_t)height;
     return RT_OK;
@@ -1834,6 +1972,8 @@ int rt_render_async(rt_ctx* ctx, int width, int height, int32_t* pixels) {
     RT_TRY(check_ctx(ctx, width, height));
     if (!pixels) return fail(ctx, RT_ERR_INVALID_ARG, "NULL pixels");
     if (ctx->rccl_gather) return rt_render(ctx, width, height, pixels);
+    TickScope tick(ctx);
+    RT_TRY(tick.begin(width, height));
     const size_t frame_bytes = (size_t)width * height * sizeof(int32_t);
     const int n = ctx->n_gpus;
     // The hand-off of frame k: by the copy engine on a second stream, chunk by chunk after each chunk's trace
@@ -1884,7 +2024,8 @@ int rt_render_async(rt_ctx* ctx, int width, int height, int32_t* pixels) {
             continue;
         }
         // (the pending hand-off as the launch's copy slice; none while it holds no words)
-        RT_TRY(trace_bands(ctx, d, d.async_stream, share_req(sh, width, height, 0, sh.nb, d.d_frames2[slot], &d.hand.job)));
+        RT_TRY(trace_bands(ctx, d, d.async_stream,
+                           share_req(sh, width, height, 0, sh.nb, d.d_frames2[slot], &d.hand.job, tick_acc(ctx, d))));
         d.hand = {};  // issued (in the launch)
         int32_t* mapped = mapped_host(ctx, g, pixels, frame_bytes);
         if (mapped) {
@@ -1895,6 +2036,7 @@ int rt_render_async(rt_ctx* ctx, int width, int height, int32_t* pixels) {
         }
         d.async_next = slot ^ 1;
     }
+    tick.done = true;
     ctx->frames++;
     ctx->pixels += (uint64_t)width * (uint64_t)height;
     return RT_OK;

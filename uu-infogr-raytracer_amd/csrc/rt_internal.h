@@ -14,6 +14,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "rt_resolve.h"
+
 namespace rtk {
 
 struct DevSphere {
@@ -280,6 +282,19 @@ struct LaunchParams {
     // Last: no other field moves.
     int foot_n;
     PlaneFoot foot[FOOT_MAX];
+    // Progressive accumulation (rt_set_progressive, the PROG instantiations): prog_acc != nullptr marks the launch.
+    // As in an ADAPT launch ss_log2 > 0, W, H and the rows are in samples, a lane is an output pixel and the grid is
+    // in output tiles.  The wave traces prog_n (0, 1 or 2) samples of every pixel of its tile -- samples prog_first
+    // and prog_first + 1 of the run, whose positions in the k x k block arrive as pass codes j k + i (sample_pixel)
+    // in prog_pass -- adds them to the pixel's sums at prog_acc[r * (W >> ss_log2) + x] (r: the launch's local output
+    // row, x: the output column; the packed band set's addressing whatever out_fmt), which it reads only when
+    // prog_first > 0 and writes only when prog_n > 0, and stores the rounded mean of the prog_first + prog_n samples
+    // (rt_resolve.h resolve_round_div) in the launch's format (rt_kernel.hip progressive_tile).  Last: no other field
+    // moves.
+    ResolveSum* prog_acc;
+    int prog_first;
+    int prog_n;
+    int prog_pass[2];
 };
 constexpr int MIRROR_BOX_PLANES = 2;
 // Tiles per workgroup of the direct kernel's single-frame launches (8: +2.5 % on C2,
@@ -304,8 +319,9 @@ enum : int { TV_DIRECT = 0, TV_BUNDLE = 1 };
 // PLAIN: pixels to `out`.  STATS: as PLAIN, and the diagnostic tallies of the executed work.  TILES: out_fmt
 // OUT_TILES, the fused tile encoder.  SS: the supersampling epilogue.  PATH: one DevView per grid z.  SHUTTER: a
 // PATH launch whose waves average 1 << shutter_log2 DevViews per grid z.  ADAPT: supersampling decided per output
-// tile (LaunchParams::adapt_thr).
-enum : int { TM_PLAIN = 0, TM_STATS = 1, TM_TILES = 2, TM_SS = 3, TM_PATH = 4, TM_SHUTTER = 5, TM_ADAPT = 6 };
+// tile (LaunchParams::adapt_thr).  PROG: one Tick of a progressive run, 0-2 samples per output pixel added to an
+// accumulator that outlives the launch (LaunchParams::prog_acc).
+enum : int { TM_PLAIN = 0, TM_STATS = 1, TM_TILES = 2, TM_SS = 3, TM_PATH = 4, TM_SHUTTER = 5, TM_ADAPT = 6, TM_PROG = 7 };
 struct TraceVariant {
     int family;  // TV_*
     int gpow;    // some material needs the f64 Math.Pow path: the entry points without the register caps
@@ -316,7 +332,7 @@ struct TraceVariant {
     int tord;    // 0: tiles in grid order (row_order / col_major), 1: tile_order, 2: as 0 and tile_cost recorded
 };
 
-enum : unsigned { VF_GPOW = 1u, VF_STATS = 2u, VF_TILES = 4u, VF_SS = 8u, VF_PATH = 16u, VF_SHUTTER = 32u, VF_ADAPT = 64u };
+enum : unsigned { VF_GPOW = 1u, VF_STATS = 2u, VF_TILES = 4u, VF_SS = 8u, VF_PATH = 16u, VF_SHUTTER = 32u, VF_ADAPT = 64u, VF_PROG = 128u };
 constexpr unsigned vf_cls(int c) { return (unsigned)c << 8; }
 constexpr unsigned vf_wpg(int w) { return (unsigned)w << 12; }
 constexpr unsigned vf_tord(int t) { return (unsigned)t << 16; }
@@ -327,7 +343,8 @@ static_assert(DIRECT_SMAX < 16 && SINGLE_WPG < 16, "the variant word's 4-bit fie
 constexpr unsigned variant_word(const TraceVariant& v) {
     return (v.gpow ? VF_GPOW : 0u) | (v.mode == TM_STATS ? VF_STATS : 0u) | (v.mode == TM_TILES ? VF_TILES : 0u) |
            (v.mode == TM_SS ? VF_SS : 0u) | (v.mode == TM_PATH ? VF_PATH : 0u) |
-           (v.mode == TM_SHUTTER ? VF_SHUTTER : 0u) | (v.mode == TM_ADAPT ? VF_ADAPT : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
+           (v.mode == TM_SHUTTER ? VF_SHUTTER : 0u) | (v.mode == TM_ADAPT ? VF_ADAPT : 0u) | (v.mode == TM_PROG ? VF_PROG : 0u) |
+           vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
 }
 
 // The bundle family's shadow pass by scene: 0 = per light (also every scene of the direct family), 1 = the
@@ -342,8 +359,8 @@ inline int merged_class(int S, int L, bool lights_a2_ok) {
 // 8-row grid when the bands are multiples of 8 output rows, or when one band covers the frame.
 inline bool adaptive_band_ok(int band_rows, int H) { return band_rows % 8 == 0 || band_rows >= H; }
 
-// The instantiations that exist (504): every mode, depth and class of both families at one tile per workgroup
-// in grid order (SHUTTER among them, under PATH's conditions, and ADAPT, under SS's: 60 of their own each); the
+// The instantiations that exist (564): every mode, depth and class of both families at one tile per workgroup
+// in grid order (SHUTTER among them, under PATH's conditions, and ADAPT and PROG, under SS's: 60 of their own each); the
 // direct kernel's lone-frame workgroups of SINGLE_WPG tiles in each tile order (PLAIN only); the all-lights-ok
 // merged bundle kernel's tile orders (PLAIN, no GPOW).
 constexpr bool trace_variant_built(const TraceVariant& v) {
@@ -358,13 +375,18 @@ constexpr bool trace_variant_built(const TraceVariant& v) {
 inline bool pick_trace_variant(const LaunchParams& p, bool generic_pow, bool stats, TraceVariant* v) {
     const bool tiles = p.out_fmt == OUT_TILES, ordered = p.tile_order != nullptr || p.tile_cost != nullptr;
     if (p.shutter_log2 != 0 && (p.views == nullptr || p.shutter_log2 < 0 || p.shutter_log2 > 8)) return false;
+    // (a progressive launch is a supersampling launch of one view, never adaptive)
+    if (p.prog_acc != nullptr && (p.views != nullptr || p.ss_log2 <= 0 || p.ss_log2 > 3 || p.adapt_thr != 0 || p.prog_first < 0 ||
+                                  p.prog_n < 0 || p.prog_n > 2 || p.prog_first + p.prog_n < 1 ||
+                                  p.prog_first + p.prog_n > 1 << (2 * p.ss_log2)))
+        return false;
     if (p.views != nullptr) {
         if (p.ss_log2 > 0 || tiles || stats || ordered || p.copy_z != 0 || p.row_order_n != 0 || p.col_major != 0)
             return false;
         v->mode = p.shutter_log2 > 0 ? TM_SHUTTER : TM_PATH;
     } else if (p.ss_log2 > 0) {
         if (p.ss_log2 > 3 || tiles || stats || ordered || p.adapt_thr < 0 || p.adapt_thr > 256) return false;
-        v->mode = p.adapt_thr > 0 ? TM_ADAPT : TM_SS;
+        v->mode = p.prog_acc != nullptr ? TM_PROG : p.adapt_thr > 0 ? TM_ADAPT : TM_SS;
     } else {
         v->mode = tiles ? TM_TILES : stats ? TM_STATS : TM_PLAIN;  // (the fused encoder never tallies)
     }

@@ -1116,6 +1116,61 @@ __device__ __forceinline__ void adaptive_tile(const LaunchParams& p, int tile_x,
     }
 }
 
+// PROG (rt_set_progressive, one Tick of a resting camera): the wave's tile is 8x8 output pixels and a lane is one of
+// them, as in an ADAPT launch, and `trace(p, pass, tile_x, tile_y)` traces sample pass = j k + i of every pixel's
+// k x k block.  The launch names 0, 1 or 2 samples (prog_n; their pass codes in prog_pass: the host knows the run's
+// sample order, rt_progressive.h); the wave traces them one after the other, adds them to the pixel's running sums
+// in LaunchParams::prog_acc -- the per-pixel accumulator that outlives the launch, 8 bytes of 16-bit fields -- and
+// stores the rounded mean of all prog_first + prog_n samples so far (rt_resolve.h resolve_round_div).
+// The loop obeys what shutter_tile and adaptive_tile found: no write to global memory inside it, ray counts reduced
+// per sample into scalars and added once after it, the tile position and the kernarg address passed through the
+// empty asm tied to the loop counter, and nothing but the counter, the sums and the wave's totals carried across a
+// trace.  The accumulator is read after the traces, and only when the run has earlier samples (prog_first > 0: the
+// launch that starts an accumulator never reads it), so its two VGPRs are not live across a trace; then one 8-byte
+// store of the new sums (prog_n > 0) and one pixel store.  With prog_n = 0 the wave only loads, rounds and stores:
+// the converged Tick's frame, by the same kernel.
+// Counting follows add_counters for a one-view launch: the frame behind a copy slice counts, when the context counts.
+template <typename F>
+__device__ __forceinline__ void progressive_tile(const LaunchParams& p, int tile_x, int tile_y, F trace) {
+    ResolveSum acc{0u, 0u};
+    unsigned n_refl = 0;
+    unsigned long long n_shadow = 0;
+#pragma unroll 1
+    for (int s = 0;; ++s) {  // wave-uniform
+        int tx = tile_x, ty = tile_y;
+        asm("" : "+s"(tx), "+s"(ty) : "s"(s));
+        const __attribute__((address_space(4))) LaunchParams* kp =
+            (const __attribute__((address_space(4))) LaunchParams*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm("" : "+s"(kp) : "s"(s));
+        const LaunchParams& q = *(const LaunchParams*)kp;
+        if (s >= q.prog_n) break;
+        const TileOut o = trace(q, q.prog_pass[s], tx, ty);
+        acc = resolve_add(acc, resolve_unpack(o.px32));
+        if (q.counters != nullptr && blockIdx.z == (unsigned)q.copy_z) {  // wave-uniform
+            n_refl += wave_count(o.cnt & CNT_REFL_MASK);
+            n_shadow += wave_count(o.cnt >> CNT_SHADOW_SHIFT);
+        }
+    }
+    const int s2 = p.ss_log2;
+    const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const TilePixel t = sample_pixel(p, tile_x, tile_y, ln, 0);  // the pixel's sample (0, 0): validity and rows
+    if (t.valid) {  // (output coordinates: r and y agree modulo k, bands are multiples of k sample rows)
+        const size_t wo = (size_t)(p.W >> s2), xo = (size_t)(t.x >> s2);
+        uint2* a = (uint2*)(p.prog_acc + ((size_t)(t.r >> s2) * wo + xo));  // (ResolveSum: 8 bytes, 8-byte aligned slots)
+        if (p.prog_first > 0) {  // wave-uniform
+            const uint2 before = *a;
+            acc = resolve_add(acc, ResolveSum{before.x, before.y});
+        }
+        if (p.prog_n > 0) *a = make_uint2(acc.rb, acc.g);
+        store_at(p, (size_t)((p.out_fmt == 2 ? t.y : t.r) >> s2) * wo + xo, resolve_round_div(acc, p.prog_first + p.prog_n));
+    }
+    if (p.counters != nullptr && blockIdx.z == (unsigned)p.copy_z && ln == 0) {
+        unsigned long long* c = &p.counters[((blockIdx.y * gridDim.x + blockIdx.x) % COUNTER_SLOTS) * COUNTER_STRIDE];
+        if (n_refl) atomicAdd(c + CNT_REFLECT, (unsigned long long)n_refl);
+        if (n_shadow) atomicAdd(c + CNT_SHADOW, n_shadow);
+    }
+}
+
 // DIRECT kernel (scenes with < CULL_MIN_SPHERES spheres).
 // STATS: the diagnostic build that also tallies the work actually executed (not timed).
 // TILES: out_fmt OUT_TILES (the fused encoder: its own instantiation, so that the others keep their
@@ -1131,7 +1186,8 @@ __device__ __forceinline__ void adaptive_tile(const LaunchParams& p, int tile_x,
 // SS: the supersampling epilogue (resolve_tile) in place of the pixel stores.  PATH: frame z of the grid takes its
 // view from LaunchParams::views (one DevView per grid z).  SHUTTER: a PATH launch whose waves trace 1 <<
 // shutter_log2 views per grid z and store their mean (shutter_tile).  ADAPT: supersampling whose waves decide per
-// 8x8 output tile whether to trace more than one sample per pixel (adaptive_tile).  All four of the plain batch
+// 8x8 output tile whether to trace more than one sample per pixel (adaptive_tile).  PROG: a progressive Tick, whose
+// waves add 0-2 samples per output pixel to the run's accumulator (progressive_tile).  All five of the plain batch
 // variants only (no STATS, no TILES, WPG 1, TORD 0: rt_internal.h trace_variant_built).
 // The options arrive as one variant word V (rt_internal.h VF_*, vf_cls = SMAX) and are read from it by name.
 template <int K, unsigned V>
@@ -1181,6 +1237,10 @@ __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
     }
     if constexpr ((V & VF_ADAPT) != 0) {
         adaptive_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int pass, int tx, int ty) { return trace_tile_direct<K, V & VF_TILE>(q, tx, ty, lv, dv, tl, pass); });
+        return;
+    }
+    if constexpr ((V & VF_PROG) != 0) {  // (a sample is traced as ADAPT's passes are: the tile trace of that word)
+        progressive_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int pass, int tx, int ty) { return trace_tile_direct<K, ((V & VF_TILE) & ~VF_PROG) | VF_ADAPT>(q, tx, ty, lv, dv, tl, pass); });
         return;
     }
     const unsigned cnt = trace_tile_direct<K, V & VF_TILE>(p, tile_x, tile_y, lv, dv, tl).cnt;
@@ -1996,6 +2056,10 @@ __device__ __forceinline__ void bundle_kernel_body(const LaunchParams& p) {
         adaptive_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int pass, int tx, int ty) { return trace_tile_bundle<K, V & VF_TILE>(q, tx, ty, stk_lv, stk_dv, tl, pass); });
         return;
     }
+    if constexpr ((V & VF_PROG) != 0) {
+        progressive_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int pass, int tx, int ty) { return trace_tile_bundle<K, ((V & VF_TILE) & ~VF_PROG) | VF_ADAPT>(q, tx, ty, stk_lv, stk_dv, tl, pass); });
+        return;
+    }
     const unsigned cnt = trace_tile_bundle<K, V & VF_TILE>(p, tile_x, tile_y, stk_lv, stk_dv, tl).cnt;
     add_counters<STATS, PATH>(p, threadIdx.x & 63, cnt & CNT_REFL_MASK, cnt >> CNT_SHADOW_SHIFT, tl);
     if (TORD == 2 && (threadIdx.x & 63) == 0 && t_rec[0].slot != nullptr)
@@ -2120,8 +2184,8 @@ __global__ __launch_bounds__(256) void scatter_gathered_kernel(const unsigned ch
 // lone frame on the direct kernel (wpg > 1) has wpg tiles of a tile row per workgroup, with the tile rows
 // in x when col_major is set, or a 1-D grid over the padded tile_order.
 static void trace_grid(const LaunchParams& p, const TraceVariant& v, dim3* grid, dim3* block) {
-    // (ADAPT: a wave is a tile of output pixels, and W, local_rows are in samples)
-    const int as = v.mode == TM_ADAPT ? p.ss_log2 : 0;
+    // (ADAPT, PROG: a wave is a tile of output pixels, and W, local_rows are in samples)
+    const int as = v.mode == TM_ADAPT || v.mode == TM_PROG ? p.ss_log2 : 0;
     const unsigned tx = (unsigned)(((p.W >> as) + TILE_W - 1) / TILE_W), ty = (unsigned)(((p.local_rows >> as) + TILE_H - 1) / TILE_H);
     const unsigned z = (unsigned)(p.n_frames > 1 ? p.n_frames : 1) + (unsigned)p.copy_z, w = (unsigned)v.wpg;
     const unsigned gxw = (tx + w - 1) / w;
@@ -2170,7 +2234,7 @@ int launch_trace(const LaunchParams& p, bool generic_pow, bool stats, void* stre
     auto leaf = [&](auto consts) { return launch_built(consts, p, grid, block, (hipStream_t)stream); };
     // (pick_trace_variant returns built descriptors only: an unbuilt one is an error, not a kernel)
     if (!peel(leaf, Vals<>{}, v.family, Vals<TV_DIRECT, TV_BUNDLE>{}, v.gpow, Vals<0, 1>{}, v.mode,
-              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
+              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT, TM_PROG>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
               Vals<1, 2, 4, 6, 8, 64>{}, v.wpg, Vals<1, SINGLE_WPG>{}, v.tord, Vals<0, 1, 2>{}))
         return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();

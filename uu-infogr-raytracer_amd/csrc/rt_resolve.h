@@ -51,6 +51,20 @@ RT_RESOLVE_FN uint32_t resolve_round_n(ResolveSum sum, int t) {
     return rb | (g << 8);
 }
 
+// Progressive accumulation (rt_set_progressive): the sum of c unpacked samples, c = 1 .. 64 -> the output pixel
+// 0x00RRGGBB, per channel (sum + c / 2) / c in integers (c / 2 floors).  No divide per field: with M = 2^21 / c + 1
+// and e = M c - 2^21 in 1..c, (n M) >> 21 = n / c for every n with n e < 2^21, and a field's n = sum + c / 2 is at
+// most 255 c + c / 2, so n e <= 255.5 c^2 < 2^20; n M < 256 * 2^21 + 2^14 stays inside 32 bits.  Integer operations
+// only, so the host's exhaustive check (tests/native/progressive_host.cpp) is the device's.  For c a power of two
+// it is resolve_round_n.
+constexpr int RESOLVE_DIV_MAX = 64;
+RT_RESOLVE_FN uint32_t resolve_round_div(ResolveSum sum, int c) {
+    const uint32_t m = (1u << 21) / (uint32_t)c + 1u, half = (uint32_t)c >> 1;
+    const uint32_t r = (((sum.rb >> 16) + half) * m) >> 21, b = (((sum.rb & 0xffffu) + half) * m) >> 21;
+    const uint32_t g = (((sum.g & 0xffffu) + half) * m) >> 21;
+    return (r << 16) | (g << 8) | b;
+}
+
 // Adaptive supersampling (rt_set_adaptive_sampling): do the pixels a and b (0x00RRGGBB) differ by at least thr,
 // thr in 1..256, in some 8-bit channel?  Per word of 16-bit fields: with bit 8 of every field of a set, a - b
 // borrows from no neighbour and the field holds 256 + (a_c - b_c) in 1..511; b - a likewise; the larger of the

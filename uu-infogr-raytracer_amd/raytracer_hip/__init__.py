@@ -152,6 +152,22 @@ class Context:
         self._check(self.lib.rt_get_adaptive_sampling(self.ptr, C.byref(t)))
         return t.value
 
+    def set_progressive(self, k: int):
+        """rt_set_progressive: k = 1 (off), 2, 4 or 8.  While the view rests, every Tick call (render, render_async,
+        render_device) adds a sample per pixel in supersample.progressive_order(k) and returns the mean so far
+        (supersample.progressive_resolve is the definition); any change of the view returns the plain frame."""
+        self._check(self.lib.rt_set_progressive(self.ptr, int(k)))
+
+    def progressive(self) -> tuple:
+        """(k, samples): the factor and the c of the frame P_c the last Tick call issued (0 before any)."""
+        k, c = C.c_int(-1), C.c_int(-1)
+        self._check(self.lib.rt_get_progressive(self.ptr, C.byref(k), C.byref(c)))
+        return k.value, c.value
+
+    def reset_progressive(self):
+        """rt_reset_progressive: the next Tick call starts a new run (the plain frame)."""
+        self._check(self.lib.rt_reset_progressive(self.ptr))
+
     def get_camera(self) -> abi.rt_camera:
         c = abi.rt_camera()
         self._check(self.lib.rt_get_camera(self.ptr, C.byref(c)))
@@ -373,13 +389,17 @@ class RayTracer:
     `samples` = 2, 4 or 8: every Tick() is supersampled k x k (Context.set_supersampling); the frame keeps its size.
     `adaptive` = 1..256 with `samples` > 1: only the tiles whose pixels differ by that much are supersampled
     (Context.set_adaptive_sampling); 0 = every pixel.
+    `progressive` = 2, 4 or 8 (with `samples` = 1): while the camera rests every Tick() adds one sample per pixel of
+    the k x k block and shows the mean so far; a Tick() after OnKeyPress / OnMouseMove moved it is the plain frame
+    (Context.set_progressive).
     """
 
     _KEYS = {"W": abi.RT_KEY_W, "A": abi.RT_KEY_A, "S": abi.RT_KEY_S, "D": abi.RT_KEY_D,
              "Space": abi.RT_KEY_SPACE, "LeftShift": abi.RT_KEY_SHIFT, "RightShift": abi.RT_KEY_SHIFT}
 
     def __init__(self, screen: Surface, scene: scenes.Scene | None = None, n_gpus: int = 1,
-                 debug: bool = False, debug_seed: int = 0, samples: int = 1, adaptive: int = 0):
+                 debug: bool = False, debug_seed: int = 0, samples: int = 1, adaptive: int = 0,
+                 progressive: int = 1):
         self.screen = screen
         self.debug = debug
         self._debug_seed = debug_seed
@@ -389,6 +409,7 @@ class RayTracer:
         self._ctx.set_scene(sc)
         self._ctx.set_supersampling(samples)
         self._ctx.set_adaptive_sampling(adaptive)
+        self._ctx.set_progressive(progressive)
         self._camera = sc.c_camera()
         self._ctx.register_host(screen.pixels)  # pin Surface.pixels once (D2H lands in it)
 

@@ -122,6 +122,9 @@ EXPORTS = [
     ("rt_get_supersampling", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("rt_set_adaptive_sampling", C.c_int, [C.c_void_p, C.c_int]),
     ("rt_get_adaptive_sampling", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("rt_set_progressive", C.c_int, [C.c_void_p, C.c_int]),
+    ("rt_get_progressive", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("rt_reset_progressive", C.c_int, [C.c_void_p]),
     ("rt_get_camera", C.c_int, [C.c_void_p, C.POINTER(rt_camera)]),
     ("rt_camera_view", C.c_int, [C.POINTER(rt_camera), C.c_int, C.c_int, C.POINTER(rt_view)]),
     ("rt_camera_on_key", C.c_int, [C.POINTER(rt_camera), C.c_int]),

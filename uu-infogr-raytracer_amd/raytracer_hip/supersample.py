@@ -71,3 +71,42 @@ def adaptive_resolve(plain: np.ndarray, samples: np.ndarray, k: int, threshold: 
     m = refine_mask(p, threshold)
     px = np.repeat(np.repeat(m, TILE, axis=0), TILE, axis=1)[:p.shape[0], :p.shape[1]]
     return np.where(px, full, p).astype(np.int32)
+
+
+# Progressive accumulation (rt_set_progressive): a resting camera's Ticks take the k x k samples of a pixel one by
+# one, coarse sub-grids first, and show the rounded mean of the samples so far.
+def progressive_order(k: int) -> list:
+    """The samples of a k x k block in the order a progressive run traces them: [(i, j)] (column, row), k*k long.
+    With s = log2 k, sample n is found from n's base-4 digits d_0 (least significant) .. d_{s-1}: digit d_t gives
+    bit s - 1 - t of i from its bit 0 and bit s - 1 - t of j from its bit 1.  The first 4^t samples are the 2^t x 2^t
+    sub-grid of stride k / 2^t."""
+    if k not in FACTORS:
+        raise ValueError(f"progressive factor {k} is not one of {FACTORS}")
+    s = k.bit_length() - 1
+    order = []
+    for n in range(k * k):
+        i = j = 0
+        for t in range(s):
+            d = (n >> (2 * t)) & 3
+            i |= (d & 1) << (s - 1 - t)
+            j |= (d >> 1) << (s - 1 - t)
+        order.append((i, j))
+    return order
+
+
+def progressive_resolve(samples_frame: np.ndarray, k: int, c: int) -> np.ndarray:
+    """The frame P_c of a progressive run: int32 0x00RRGGBB frame [k H, k W] (the frame at k W x k H, which holds
+    every sample) -> int32 [H, W], per channel (sum of samples 0 .. c-1 of progressive_order(k) + c // 2) // c."""
+    order = progressive_order(k)
+    if not 1 <= int(c) <= k * k:
+        raise ValueError(f"sample count {c} is not in 1..{k * k}")
+    f = np.asarray(samples_frame)
+    if f.ndim != 2 or f.shape[0] % k or f.shape[1] % k:
+        raise ValueError(f"a 2-D frame with sides that are multiples of {k} is required, got {f.shape}")
+    f = f.astype(np.int64)
+    out = np.zeros((f.shape[0] // k, f.shape[1] // k), dtype=np.int64)
+    for shift in (16, 8, 0):
+        ch = (f >> shift) & 0xFF
+        total = sum(ch[j::k, i::k] for i, j in order[:c])
+        out |= ((total + c // 2) // c) << shift
+    return out.astype(np.int32)
