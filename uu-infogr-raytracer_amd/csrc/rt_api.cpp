@@ -437,6 +437,7 @@ void scene_params(const rt_ctx* ctx, const Device& d, LaunchParams& lp) {
     lp.n_clus = L.n_clus;
     lp.S = L.S, lp.P = L.P, lp.L = L.L, lp.limit = L.limit;
     lp.lights_a2_ok = L.lights_a2_ok ? 1 : 0;
+    lp.uniform_plane = L.uniform_plane ? 1 : 0;
     lp.counters = ctx->counting ? d.d_counters : nullptr;  // nullptr: the kernels count nothing (rt_set_counting)
 }
 
@@ -1136,6 +1137,7 @@ int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_
     opt.mirror_box = !off("RT_MIRROR_BOX");
     opt.dark_skip = !off("RT_DARK_SKIP");
     opt.prim_foot = !off("RT_PRIM_FOOT");
+    opt.uniform_plane = !off("RT_UNIFORM_PLANE");
     SceneLayout L = scene_build(spheres, n_spheres, planes, n_planes, lights, n_lights, ambient, recursion_limit, opt);
     for (Device& d : ctx->dev) {
         DeviceGuard guard(d.id);

@@ -295,6 +295,11 @@ struct LaunchParams {
     int prog_first;
     int prog_n;
     int prog_pass[2];
+    // Plane-uniform waves (the direct kernel, rt_kernel.hip trace_tile_direct; where operands come from, never what
+    // is computed): 1: a wave whose level-0 records all lie on one plane shades them converged, with that plane's
+    // material and geometry read through a wave-uniform index; 0: no wave is classified (a zeroed block, and
+    // RT_UNIFORM_PLANE=0 through rt_set_scene).  Last: no other field moves.
+    int uniform_plane;
 };
 constexpr int MIRROR_BOX_PLANES = 2;
 // Tiles per workgroup of the direct kernel's single-frame launches (8: +2.5 % on C2,

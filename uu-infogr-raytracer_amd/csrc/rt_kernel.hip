@@ -282,6 +282,13 @@ struct ScratchStack {
         x = a[n];
         y = b[n];
     }
+    // the level-0 record (n >= 1), as pop hands it out; the stack is left as it is
+    template <int PATH = VIEW_ARGS>
+    __device__ __forceinline__ void level0(const LaunchParams&, float4& x, float4& y, int = 0) {
+        x = a[0];
+        y = b[0];
+    }
+    __device__ __forceinline__ int code0() const { return __float_as_int(b[0].w); }  // level 0's primitive code
 };
 
 // One reflection step of the forward walk (TraceSphere :854 / TracePlane normal,
@@ -341,6 +348,18 @@ struct LdsStack {
         x = make_float4(hp.x, hp.y, hp.z, tk.x);
         y = make_float4(d.x, d.y, d.z, tk.y);
     }
+    // the level-0 record (n >= 1) without a re-walk: pop's own operations at n = 0 -- the camera, the primary
+    // direction, hp = cam + d t -- and no loop; the stack is left as it is
+    template <int PATH = VIEW_ARGS>
+    __device__ __forceinline__ void level0(const LaunchParams& p, float4& x, float4& y, int rec = 0) {
+        const f3 o = ViewOf<PATH>{p, rec}.cam();
+        const f3 d = mk(dv[(threadIdx.x & 63)], dv[WG_THREADS + (threadIdx.x & 63)], dv[2 * WG_THREADS + (threadIdx.x & 63)]);
+        const float2 tk = lv[(threadIdx.x & 63)];
+        const f3 hp = add(o, scale(d, tk.x));
+        x = make_float4(hp.x, hp.y, hp.z, tk.x);
+        y = make_float4(d.x, d.y, d.z, tk.y);
+    }
+    __device__ __forceinline__ int code0() const { return __float_as_int(lv[(threadIdx.x & 63)].y); }  // level 0's primitive code
 };
 
 // Stack type per K (= recursion limit + 1 records): the LDS stack up to 8 levels (A/B round 1:
@@ -472,6 +491,12 @@ __device__ __forceinline__ void add_counters(const LaunchParams& p, int lane, un
         }
     }
 }
+
+// Plane-uniform waves of the direct kernel (trace_tile_direct), A/B builds: RT_UNIFORM_PLANE=0 compiles the
+// classification and the converged level-0 fold out.
+#ifndef RT_UNIFORM_PLANE
+#define RT_UNIFORM_PLANE 1
+#endif
 
 // Result of a nearest-hit search.
 struct Hit {
@@ -677,6 +702,18 @@ __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere
     // (the nominal count: shaded diffuse hits x lights, dark or not)
     if (flags & MAT_DIFFUSE) *n_shadow += (unsigned)p.L << CNT_SHADOW_SHIFT;
     return add(col, mk(m.amb[0], m.amb[1], m.amb[2]));
+}
+
+// Level 0 of a plane-uniform wave (trace_tile_direct): shade_direct's plane arm for a plane index `plane` that is the
+// same on every active lane.  The same operations in the same order -- it is that function, inlined a second time
+// with is_sphere the constant false and a wave-uniform index: the sphere arm is gone, the material and plane
+// records arrive by scalar loads, and the flag tests and the exponent switch are scalar branches.  The dark-square
+// test, the light loop, the shadow scans, the clamps and the counts stay per lane.  Converged call on the wave's
+// level-0 lanes.
+template <typename T>
+__device__ __forceinline__ f3 shade_plane_uniform(const LaunchParams& p, int plane, f3 hp, f3 d, float t, f3 sec,
+                                                  unsigned* n_shadow, T& tl) {
+    return shade_direct<false>(p, false, plane, hp, d, t, sec, n_shadow, tl);
 }
 
 // Candidate spheres of a wave's primary rays: those whose per-frame screen box (view_params)
@@ -898,12 +935,15 @@ struct TileOut {
 // DIRECT path, one 8x8 tile: each lane walks its own chain with per-lane (divergent) control
 // flow.  rec: the sub-frame's view record (SHUTTER, wave-uniform; see ViewOf), or the sample pass (ADAPT, wave-uniform;
 // sample_pixel) -- the ADAPT kernels have the one view of the launch parameters and ViewOf never reads it.
-template <int K, unsigned V, typename T>
+template <int K, unsigned V, bool UNIFORM_OK = true, typename T>
 __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
                                                      float* stk_dv, T& tl, int rec = 0) {
     constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = (V & VF_SS) != 0, SHUTTER = (V & VF_SHUTTER) != 0;
     constexpr bool ADAPT = (V & VF_ADAPT) != 0;
     constexpr int PATH = view_of(V);
+    // plane-uniform waves: not in the GPOW kernels, where a second inlined pow costs an occupancy step, nor where the
+    // kernel body says so (UNIFORM_OK)
+    constexpr bool UNIFORM = RT_UNIFORM_PLANE && UNIFORM_OK && !GPOW;
     const int lane = threadIdx.x & 63;
     const TilePixel tpx = ADAPT ? sample_pixel(p, tile_x, tile_y, lane, rec)
                                 : tile_pixel<SS>(p, tile_x * TILE_W + (lane & 7), tile_y * TILE_H + (lane >> 3));
@@ -970,14 +1010,39 @@ __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int 
             // record each, so K = limit + 1 records suffice).  Per lane, divergent: the bundle
             // kernel's converged fold with wave-level shadow culling measured slower here (C2
             // +14 %, C3 +17 %, profiles/ab/r02_direct_converged_fold_rejected.txt)
+            // Plane-uniform waves: the lanes with a record (stk.n > 0) are those that pushed a level-0 one, and the
+            // wave is plane-uniform when there is such a lane and every one of them hit the plane of the first -- read
+            // back from the stack, so that nothing of the test is live across the walk.  Lanes that missed or were
+            // too close stay outside; a sphere silhouette or a seam between two planes in the tile leaves the wave to
+            // the per-lane code.  A plane-uniform wave folds down to level 1 that way (floor_n, wave-uniform),
+            // reconverges on its level-0 lanes and shades level 0 once, with the lane's folded colour (`leaf`
+            // without a deeper record) as the mirror term's input.
+            int floor_n = 0;
+            if constexpr (UNIFORM) {
+                const bool rec0 = stk.n > 0;
+                const unsigned long long m0 = __builtin_amdgcn_ballot_w64(rec0);
+                if (p.uniform_plane && m0 != 0) {  // wave-uniform
+                    const int code = rec0 ? stk.code0() : 0;
+                    const int code0 = __builtin_amdgcn_readlane(code, (int)__builtin_ctzll(m0));
+                    if (code0 < 0 && __builtin_amdgcn_ballot_w64(rec0 && code != code0) == 0) floor_n = 1;
+                }
+            }
             f3 col = leaf;
-            while (stk.n > 0) {
+            while (stk.n > floor_n) {
                 float4 ra, rb;
                 stk.template pop<PATH>(p, ra, rb, rec);
                 const int code = __float_as_int(rb.w);
                 const bool is_s = code >= 0;
                 col = shade_direct<GPOW>(p, is_s, is_s ? code : ~code, mk(ra.x, ra.y, ra.z),
                                                mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl);
+            }
+            if constexpr (UNIFORM) {
+                if (floor_n != 0 && stk.n != 0) {  // the level-0 lanes of a plane-uniform wave
+                    float4 ra, rb;
+                    stk.template level0<PATH>(p, ra, rb, rec);
+                    const int plane = ~__builtin_amdgcn_readfirstlane(__float_as_int(rb.w));
+                    col = shade_plane_uniform(p, plane, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl);
+                }
             }
             px32 = (shift_channel(col.x) << 16) | (shift_channel(col.y) << 8) | shift_channel(col.z);
         }
@@ -1243,7 +1308,9 @@ __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
         progressive_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int pass, int tx, int ty) { return trace_tile_direct<K, ((V & VF_TILE) & ~VF_PROG) | VF_ADAPT>(q, tx, ty, lv, dv, tl, pass); });
         return;
     }
-    const unsigned cnt = trace_tile_direct<K, V & VF_TILE>(p, tile_x, tile_y, lv, dv, tl).cnt;
+    // (the launches that record tile durations, TORD 2, run below 8 waves per SIMD already and would lose another step
+    // to the plane-uniform path: they trace without it)
+    const unsigned cnt = trace_tile_direct<K, V & VF_TILE, TORD != 2>(p, tile_x, tile_y, lv, dv, tl).cnt;
     add_counters<STATS, PATH>(p, threadIdx.x & 63, cnt & CNT_REFL_MASK, cnt >> CNT_SHADOW_SHIFT, tl);
     if (TORD == 2 && (threadIdx.x & 63) == 0) {
         const TileRec r = t_rec[threadIdx.x >> 6];

@@ -77,6 +77,7 @@ struct SceneLayout {
     bool has_shpre = false;  // the direct kernel's shadow pre-test records (DevShadowCull [L][S + (S & 1)])
     bool mirror_box = true;  // the direct kernel's mirrored screen boxes (view_mirror_boxes); RT_MIRROR_BOX=0: off
     bool prim_foot = true;   // the direct kernel's plane footprints (rt_foot.h, view_build); RT_PRIM_FOOT=0: off
+    bool uniform_plane = true;  // the direct kernel's plane-uniform waves (LaunchParams::uniform_plane); RT_UNIFORM_PLANE=0: off
     int n_clus = 0;  // DevCluster records (the bundle kernel's per-lane pre-cull), 0: none
     bool has_shcull = false;
     bool has_shg = false;  // per-light shadow grids (DevShadowGrid) for the merged shadow pass
@@ -94,6 +95,7 @@ struct SceneOptions {
     bool mirror_box = true;   // RT_MIRROR_BOX=0: no mirrored screen boxes (SceneLayout::mirror_box)
     bool dark_skip = true;    // RT_DARK_SKIP=0: MAT_DARK_OK stays clear
     bool prim_foot = true;    // RT_PRIM_FOOT=0: no plane footprints (SceneLayout::prim_foot)
+    bool uniform_plane = true;  // RT_UNIFORM_PLANE=0: no wave is plane-uniform (SceneLayout::uniform_plane)
     int cluster_size = CLUSTER_SIZE;  // RT_TRACE_CLUSTERS=0: no clusters, =2..16: spheres per cluster
 };
 
@@ -449,6 +451,8 @@ inline SceneLayout scene_build(const rt_sphere* spheres, int n_spheres, const rt
     }
     // the plane footprints of a view (rt_foot.h, built per view by view_build); RT_PRIM_FOOT=0 turns them off (A/B)
     L.prim_foot = opt.prim_foot;
+    // the direct kernel's plane-uniform waves (rt_kernel.hip trace_tile_direct); RT_UNIFORM_PLANE=0 turns them off (A/B)
+    L.uniform_plane = opt.uniform_plane;
     // the dark-tile skip (rt_dark.h): planes whose material and the scene's lights pass the host part of its guard;
     // RT_DARK_SKIP=0 leaves the bit clear (A/B)
     if (opt.dark_skip)
