@@ -434,6 +434,7 @@ void scene_params(const rt_ctx* ctx, const Device& d, LaunchParams& lp) {
     lp.shslab = L.has_shg ? (const unsigned long long*)(base + L.off_shslab) : nullptr;
     lp.clus = L.n_clus ? (const DevCluster*)(base + L.off_clus) : nullptr;
     lp.shpre = L.has_shpre ? (const DevShadowCull*)(base + L.off_shpre) : nullptr;
+    lp.shgrp = L.has_shgrp ? (const DevShadowGroups*)(base + L.off_shgrp) : nullptr;
     lp.n_clus = L.n_clus;
     lp.S = L.S, lp.P = L.P, lp.L = L.L, lp.limit = L.limit;
     lp.lights_a2_ok = L.lights_a2_ok ? 1 : 0;
@@ -1134,6 +1135,7 @@ int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_
     opt.shadow_grid = !off("RT_SHADOW_GRID");
     if (const char* cv = std::getenv("RT_TRACE_CLUSTERS")) opt.cluster_size = std::atoi(cv);
     opt.shadow_pre = !off("RT_SHADOW_PRE");
+    opt.shadow_groups = !off("RT_SHADOW_GROUPS");
     opt.mirror_box = !off("RT_MIRROR_BOX");
     opt.dark_skip = !off("RT_DARK_SKIP");
     opt.prim_foot = !off("RT_PRIM_FOOT");

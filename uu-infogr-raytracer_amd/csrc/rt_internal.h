@@ -94,6 +94,22 @@ constexpr long long SHADOW_CULL_MAX_ENTRIES = 1LL << 16;
 // The direct kernel's per-lane shadow pre-test (S < CULL_MIN_SPHERES; culling only): per (light, sphere) the
 // centre's (u, v) in the light's frame and, with the sphere's share of the margin folded in, the axial bound
 // ca' and the radius bound rr' (rt_api.cpp, rt_kernel.hip shadow_pre_keep).  Same record type, [L][S + (S & 1)].
+//
+// Per-light bounding hierarchy over those records (rt_scene.h build_shadow_groups; culling only): the spheres of a
+// light are split into at most SHADOW_GROUPS groups by closeness in the light's (u, v), each with a record of the
+// same shape -- a disc that contains its members' discs, the largest of their ca' -- and the members as a mask over
+// sphere indices (S < CULL_MIN_SPHERES <= 16); `uni` contains every group the same way.  A plane-uniform wave tests
+// the union before the pair loop (rt_kernel.hip shadow_scan, rt_shadow_pre.h); the group level is built and checked
+// (tests/native/shadow_group_host.cpp) and not read by the kernel (profiles/ab/r15_shadow_groups.txt).  A group
+// without members has mask 0 and a record no finite lane keeps.  [L], behind the pre-test records.
+constexpr int SHADOW_GROUPS = 3;
+struct DevShadowGroups {
+    DevShadowCull uni;
+    DevShadowCull grp[SHADOW_GROUPS];
+    uint32_t mask[SHADOW_GROUPS];
+    uint32_t pad;
+};
+static_assert(sizeof(DevShadowGroups) % 16 == 0, "DevShadowGroups records are 16-byte aligned in the scene image");
 
 // Per-light shadow grid (bundle kernel's merged shadow pass, S <= 64 spheres, L <= 4 lights;
 // culling only).  Every shadow ray of light l has direction p_l, so whether sphere j can block a
@@ -300,6 +316,10 @@ struct LaunchParams {
     // material and geometry read through a wave-uniform index; 0: no wave is classified (a zeroed block, and
     // RT_UNIFORM_PLANE=0 through rt_set_scene).  Last: no other field moves.
     int uniform_plane;
+    // The shadow pre-test's group and union records (DevShadowGroups [L]; the direct kernel's plane-uniform waves;
+    // culling only), or nullptr: the flat loop over every pair (no pre-test records, RT_SHADOW_GROUPS=0 through
+    // rt_set_scene, a zeroed block).  Last: no other field moves.
+    const DevShadowGroups* shgrp;
 };
 constexpr int MIRROR_BOX_PLANES = 2;
 // Tiles per workgroup of the direct kernel's single-frame launches (8: +2.5 % on C2,

@@ -31,6 +31,7 @@
 #include "rt_pow.h"
 #include "rt_prims.h"
 #include "rt_resolve.h"
+#include "rt_shadow_pre.h"
 
 // One wave (64 lanes, an 8x8 pixel tile) per workgroup: a one-wave group releases its LDS
 // stack slots as soon as it ends.  The dispatcher launches one-wave groups no faster than
@@ -497,6 +498,11 @@ __device__ __forceinline__ void add_counters(const LaunchParams& p, int lane, un
 #ifndef RT_UNIFORM_PLANE
 #define RT_UNIFORM_PLANE 1
 #endif
+// The shadow pre-test's group records in those waves (shadow_scan's GROUPS), A/B builds: RT_SHADOW_GROUPS=0 compiles
+// the hierarchical path out.
+#ifndef RT_SHADOW_GROUPS
+#define RT_SHADOW_GROUPS 1
+#endif
 
 // Result of a nearest-hit search.
 struct Hit {
@@ -584,36 +590,28 @@ __device__ __forceinline__ void for_sphere_pairs(const LaunchParams& p, F body) 
 // scan), and on C2/C3 most spheres are kept by no lane of the wave (C3 -7.8 %, C2 -4.0 % per frame,
 // profiles/ab/r06_direct_shadow_pre.txt).
 //
-// The pre-test (culling only, FMA allowed): shadow_sphere_cull's line and behind rules for a single ray (R = 0)
-// from the lane's hit point, with the margin split into the lane part m_l and the sphere part folded into the
-// record (rt_api.cpp build_shadow_pre: rules, margins, exactness).  A lane whose |O_f|_1 is 2^38 or more (or
-// NaN) keeps every sphere (m_l = +inf).
-struct ShadowPreLane {
-    float ou, ov, oa, ml;
-};
-__device__ __forceinline__ ShadowPreLane shadow_pre_lane(f3 hp, const DevLight& l) {
-    ShadowPreLane q;
-    q.ou = __builtin_fmaf(hp.z, l.uz, __builtin_fmaf(hp.y, l.uy, hp.x * l.ux));
-    q.ov = __builtin_fmaf(hp.z, l.vz, __builtin_fmaf(hp.y, l.vy, hp.x * l.vx));
-    q.oa = __builtin_fmaf(hp.z, l.az, __builtin_fmaf(hp.y, l.ay, hp.x * l.ax));
-    const float l1 = __builtin_fabsf(q.ou) + __builtin_fabsf(q.ov) + __builtin_fabsf(q.oa);
-    q.ml = l1 < 0x1p38f ? __builtin_fmaf(l1, 0x1.01p-8f, 0x1p-30f) : __builtin_inff();
-    return q;
-}
-// true: sphere e may block this lane's shadow ray (NaN anywhere: kept)
-__device__ __forceinline__ bool shadow_pre_keep(const ShadowPreLane& q, const DevShadowCull& e) {
-    const float wu = e.cu - q.ou, wv = e.cv - q.ov;
-    const float T = e.rr + q.ml;
-    const bool line = __builtin_fmaf(wu, wu, wv * wv) > T * T;
-    const bool behind = q.oa - e.ca > q.ml;
-    return !(line || behind);
-}
-
-template <bool A2OK, typename T>
+// The pre-test itself (ShadowPreLane, shadow_pre_lane, shadow_pre_keep) lives in rt_shadow_pre.h, shared with the
+// host check of the records.
+//
+// GROUPS (the converged level 0 of a plane-uniform wave, with the scene's group records p.shgrp): a scanning floor
+// wave runs S per-lane pre-tests per light and on C3 about 15.7 of its 16 only establish that nothing is near.  The
+// union record of the light's bounding hierarchy (DevShadowGroups, rt_scene.h build_shadow_groups: the proof) is
+// tested first, by the same function with the lane margin widened once: no lane keeps the union -- not blocked, no
+// sphere visited; otherwise the flat loop as it stands.  A sphere some lane's pre-test keeps keeps the union, so the
+// same spheres are tested exactly, in the same ascending order: pixels, ray counts and the tallies are unchanged.
+// The group level on top (a member mask from the three group records, pairs outside it skipped) gained no more on C3
+// and cost the scan without records 0.3 us in spilled SGPRs and serial scalar loads: profiles/ab/r15_shadow_groups.txt.
+template <bool A2OK, bool GROUPS, typename T>
 __device__ __forceinline__ bool shadow_scan(const LaunchParams& p, f3 hp, const DevLight& l, int li, T& tl) {
     int blk = 0;
     if (A2OK && p.shpre != nullptr) {  // wave-uniform
-        const ShadowPreLane q = shadow_pre_lane(hp, l);
+        const ShadowPreLane q = shadow_pre_lane(hp.x, hp.y, hp.z, l);
+        if constexpr (GROUPS) {
+            // wave-uniform: no lane keeps the union of the light's discs -- not blocked, no sphere visited
+            if (p.shgrp != nullptr &&
+                __builtin_amdgcn_ballot_w64(shadow_pre_keep(shadow_pre_widen(q, SHADOW_UNION_WIDEN), p.shgrp[li].uni)) == 0)
+                return false;
+        }
         const DevShadowCull* e = p.shpre + (size_t)li * (size_t)(p.S + (p.S & 1));
         for_sphere_pairs<T>(p, [&](int i) {
             const DevShadowCull e0 = e[i], e1 = e[i + 1];
@@ -639,7 +637,7 @@ __device__ __forceinline__ bool shadow_scan(const LaunchParams& p, f3 hp, const 
     return blk != 0;
 }
 
-template <bool GPOW, typename T>
+template <bool GPOW, bool GROUPS = false, typename T>
 __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere, int prim, f3 hp, f3 d, float t, f3 sec,
                                            unsigned* n_shadow, T& tl) {
     const DevMaterial& m = p.mat[is_sphere ? prim : p.S + prim];
@@ -687,7 +685,7 @@ __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere
             bool blocked = false;
             if (shadow_matters(ph, l.intensity, att)) {
                 tl.shadow(true);
-                blocked = l_ok ? shadow_scan<true>(p, hp, l, li, tl) : shadow_scan<false>(p, hp, l, li, tl);
+                blocked = l_ok ? shadow_scan<true, GROUPS>(p, hp, l, li, tl) : shadow_scan<false, false>(p, hp, l, li, tl);
             }
             const float inten = blocked ? 0.0f : l.intensity;
             const float ia = inten * att;
@@ -713,7 +711,7 @@ __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere
 template <typename T>
 __device__ __forceinline__ f3 shade_plane_uniform(const LaunchParams& p, int plane, f3 hp, f3 d, float t, f3 sec,
                                                   unsigned* n_shadow, T& tl) {
-    return shade_direct<false>(p, false, plane, hp, d, t, sec, n_shadow, tl);
+    return shade_direct<false, RT_SHADOW_GROUPS != 0>(p, false, plane, hp, d, t, sec, n_shadow, tl);
 }
 
 // Candidate spheres of a wave's primary rays: those whose per-frame screen box (view_params)

@@ -75,6 +75,8 @@ struct SceneLayout {
     size_t off_sph = 0, off_mat = 0, off_pl = 0, off_li = 0, off_cull = 0, off_shcull = 0, bytes = 0;
     size_t off_shg = 0, off_shgrid = 0, off_shslab = 0, off_clus = 0, off_shpre = 0;
     bool has_shpre = false;  // the direct kernel's shadow pre-test records (DevShadowCull [L][S + (S & 1)])
+    size_t off_shgrp = 0;
+    bool has_shgrp = false;  // their group and union records (DevShadowGroups [L]); RT_SHADOW_GROUPS=0: none
     bool mirror_box = true;  // the direct kernel's mirrored screen boxes (view_mirror_boxes); RT_MIRROR_BOX=0: off
     bool prim_foot = true;   // the direct kernel's plane footprints (rt_foot.h, view_build); RT_PRIM_FOOT=0: off
     bool uniform_plane = true;  // the direct kernel's plane-uniform waves (LaunchParams::uniform_plane); RT_UNIFORM_PLANE=0: off
@@ -92,6 +94,7 @@ struct SceneLayout {
 struct SceneOptions {
     bool shadow_grid = true;  // RT_SHADOW_GRID=0: no shadow grids (the merged pass keeps the per-level bound)
     bool shadow_pre = true;   // RT_SHADOW_PRE=0: no shadow pre-test records
+    bool shadow_groups = true;  // RT_SHADOW_GROUPS=0: no group and union records over them (the flat pair loop)
     bool mirror_box = true;   // RT_MIRROR_BOX=0: no mirrored screen boxes (SceneLayout::mirror_box)
     bool dark_skip = true;    // RT_DARK_SKIP=0: MAT_DARK_OK stays clear
     bool prim_foot = true;    // RT_PRIM_FOOT=0: no plane footprints (SceneLayout::prim_foot)
@@ -154,6 +157,164 @@ inline void build_shadow_pre(const DevLight* li, int n_lights, const DevSphereCu
             e.ca = std::nextafter((float)((double)(float)ca + mc), INFINITY);
             e.rr = std::nextafter((float)((double)cull[i].rr + 0x1p-18 * clen + mc), INFINITY);
         }
+    }
+}
+
+// The smallest disc that contains the discs (x[i], y[i], r[i]), i in idx (not empty; finite values), to within
+// 2^-30 of their box: centre (*cx, *cy); the caller derives the radius from the centre it stores.  When the disc
+// spanned by the pair with the largest span -- or the largest member alone -- contains every member, it is the
+// answer; otherwise f(c) = max_i |c - c_i| + r_i is convex in c and a nested ternary search over the box of the
+// centres finds its minimum.
+inline void enclosing_disc(const double* x, const double* y, const double* r, const std::vector<int>& idx, double* cx, double* cy) {
+    auto far = [&](double px, double py) {
+        double f = 0.0;
+        for (int i : idx) f = std::max(f, std::hypot(x[i] - px, y[i] - py) + r[i]);
+        return f;
+    };
+    double bx = x[idx[0]], by = y[idx[0]], br = r[idx[0]];
+    double x0 = bx, x1 = bx, y0 = by, y1 = by;
+    for (int i : idx) {
+        if (r[i] > br) bx = x[i], by = y[i], br = r[i];
+        x0 = std::min(x0, x[i]), x1 = std::max(x1, x[i]), y0 = std::min(y0, y[i]), y1 = std::max(y1, y[i]);
+    }
+    for (int i : idx)
+        for (int j : idx) {
+            const double d = std::hypot(x[j] - x[i], y[j] - y[i]);
+            const double span = 0.5 * (d + r[i] + r[j]);
+            if (j <= i || !(d > 0.0) || span <= br || span <= r[i] || span <= r[j]) continue;
+            const double t = (span - r[i]) / d;  // the centre lies span - r_i from c_i toward c_j
+            bx = x[i] + (x[j] - x[i]) * t, by = y[i] + (y[j] - y[i]) * t, br = span;
+        }
+    *cx = bx, *cy = by;
+    if (far(bx, by) <= br * (1.0 + 0x1p-40)) return;
+    auto best_y = [&](double px, double* py) {
+        double lo = y0, hi = y1;
+        for (int k = 0; k < 52; ++k) {
+            const double a = lo + (hi - lo) / 3.0, b = hi - (hi - lo) / 3.0;
+            if (far(px, a) <= far(px, b)) hi = b; else lo = a;
+        }
+        *py = 0.5 * (lo + hi);
+        return far(px, *py);
+    };
+    double lo = x0, hi = x1, py = by;
+    for (int k = 0; k < 52; ++k) {
+        const double a = lo + (hi - lo) / 3.0, b = hi - (hi - lo) / 3.0;
+        if (best_y(a, &py) <= best_y(b, &py)) hi = b; else lo = a;
+    }
+    const double px = 0.5 * (lo + hi);
+    if (best_y(px, &py) < far(bx, by)) *cx = px, *cy = py;
+}
+
+// The record (DevShadowCull-shaped) that contains the records m[0..n) -- members of a group, or the groups of a light:
+// centre near the centre of the smallest disc enclosing their discs, rounded to binary32; rr >= max_i (|c - c_i| +
+// rr_i) (1 + 2^-16), from the rounded centre, in double, rounded up; ca = max_i ca_i.  A member without a usable
+// record (rr or ca not finite) gives {0, 0, +inf, +inf}: always kept; n = 0 gives {+inf, 0, 0, 0}: never kept by a
+// lane with a finite margin (the padding sphere's record).
+inline DevShadowCull shadow_enclose(const DevShadowCull* m, int n) {
+    if (n == 0) return DevShadowCull{INFINITY, 0.0f, 0.0f, 0.0f};
+    std::vector<double> x((size_t)n), y((size_t)n), r((size_t)n);
+    std::vector<int> idx((size_t)n);
+    float ca = -INFINITY;
+    for (int i = 0; i < n; ++i) {
+        if (!(std::isfinite(m[i].rr) && std::isfinite(m[i].ca) && std::isfinite(m[i].cu) && std::isfinite(m[i].cv)))
+            return DevShadowCull{0.0f, 0.0f, INFINITY, INFINITY};
+        x[(size_t)i] = m[i].cu, y[(size_t)i] = m[i].cv, r[(size_t)i] = m[i].rr, idx[(size_t)i] = i;
+        ca = std::max(ca, m[i].ca);
+    }
+    double cx = 0.0, cy = 0.0;
+    enclosing_disc(x.data(), y.data(), r.data(), idx, &cx, &cy);
+    DevShadowCull e;
+    e.cu = (float)cx, e.cv = (float)cy, e.ca = ca;
+    double rr = 0.0;
+    for (int i = 0; i < n; ++i) rr = std::max(rr, std::hypot(x[(size_t)i] - (double)e.cu, y[(size_t)i] - (double)e.cv) + r[(size_t)i]);
+    e.rr = std::nextafter(up(rr * (1.0 + 0x1p-16)), INFINITY);
+    return e;
+}
+
+// The group and union records of the shadow pre-test (DevShadowGroups [L], rt_internal.h; culling only), from each
+// light's finished pre-test records `pre` ([L][s_pad], build_shadow_pre).
+//
+// Groups: the spheres without a usable record (ca' = rr' = +inf) form one group; the others start as one group each
+// and the two whose discs span the least (complete linkage on (d_ij + rr_i + rr_j) / 2) merge until at most
+// `groups` remain in all.  The padding sphere of an odd count is in no group.  Every group's record is
+// shadow_enclose of its members, the union's is shadow_enclose of the group records; a group with an unusable member
+// and the union over it are +inf.  The masks are disjoint and cover exactly the spheres 0..S-1.
+//
+// Soundness.  The kernel skips sphere i for a wave when no lane keeps the union, or no lane keeps i's group; it must
+// skip only spheres that shadow_pre_keep(q, member i) drops on every lane.  So for every lane record q that
+// shadow_pre_lane makes (m_l = +inf, or every coordinate finite with |O_f|_1 < 2^38 and 2^-30 <= m_l < 2^31):
+//     keep(q, member)  =>  keep(widen(q, 1 + 2^-10), its group)  =>  keep(widen(q, 1 + 2^-9), union),
+// with keep = !(line || behind); it suffices that each rule of the enclosing record implies the rule of the enclosed.
+// m_l = +inf: T = +inf, T T = +inf and nothing exceeds it; oa - ca > +inf never holds: every record is kept.
+// A +inf record likewise keeps every lane.  An empty group has mask 0.  Otherwise, with u = 2^-24, records e (inner,
+// margin m) and g (outer, margin m' = fl(m k), k >= (1 + 2^-10) m-ratio of the two levels):
+//   behind: ca_g >= ca_e, binary32 subtraction is monotonic, so fl(oa - ca_g) <= fl(oa - ca_e); and m' >= m because
+//     rounding is monotonic and m k >= m.  fl(oa - ca_g) > m'  =>  fl(oa - ca_e) > m.
+//   line: let D be the true distance of (ou, ov) from a record's centre and T^ = rr + m in the reals.  |C_f|_1 and
+//     |O_f|_1 are below 2^38 and an enclosing centre lies in the box of its members', so |w| < 2^40, s cannot
+//     overflow, and the computed s = fl(fma(wu, wu, fl(wv wv))) lies within D^2 (1 +- u)^4 -+ 2^-149 (the one
+//     product that can underflow); T^ >= 2^-30, so fl(fl(T^)^2) lies within T^^2 (1 +- u)^3, or it
+//     overflows to +inf (rr' of a huge sphere): then no line rule holds for this record, nor for a record that
+//     encloses it, whose fl(T^) is no smaller (rr_g + m' >= rr_e + m, rounding is monotonic).  Hence
+//         line  =>  D > T^ (1 - 2^-21)        and        D > T^ (1 + 2^-21)  =>  line
+//     (2^-149 is far below 2^-21 T^^2 >= 2^-81).  With d the distance of the two centres, D_e >= D_g - d:
+//         line_g  =>  D_e > (rr_g + m')(1 - 2^-21) - d.
+//     rr_g >= (d + rr_e)(1 + 2^-16) gives rr_g (1 - 2^-21) >= d + rr_e (1 + 2^-21) -- a relative inflation covers
+//     the record's own term -- and m' >= m (1 + 2^-10)(1 - u) gives m' (1 - 2^-21) >= m (1 + 2^-21): the lane
+//     margin, which can be large against rr at distant hit points (m_l = 2^-8 |O|_1), is covered by widening it, not
+//     by rr.  So D_e > (rr_e + m)(1 + 2^-21): line_e.  (d and rr are evaluated in double from the stored binary32
+//     centres: errors of 2^-50 relative, against the 2^-16 allowed.)
+//   The union's margin k = 1 + 2^-9 is the group margin times at least (1 + 2^-10)(1 - 2^-11) > 1 + 2^-11, which
+//   the same step needs only to exceed (1 + 2^-21)(1 + u)^2 / (1 - 2^-21).
+// tests/native/shadow_group_host.cpp checks the chain in binary32 with the kernel's functions.
+inline void build_shadow_groups(const DevShadowCull* pre, int n_lights, int n_spheres, int s_pad, DevShadowGroups* out,
+                                int groups = SHADOW_GROUPS) {
+    groups = std::max(1, std::min(groups, SHADOW_GROUPS));
+    for (int j = 0; j < n_lights; ++j) {
+        const DevShadowCull* e = pre + (size_t)j * (size_t)s_pad;
+        DevShadowGroups& g = out[j];
+        std::memset(&g, 0, sizeof g);
+        std::vector<std::vector<int>> cl;
+        std::vector<int> bad;
+        for (int i = 0; i < n_spheres; ++i) {
+            if (std::isfinite(e[i].rr) && std::isfinite(e[i].ca)) cl.push_back(std::vector<int>(1, i));
+            else bad.push_back(i);
+        }
+        const size_t room = (size_t)groups - (bad.empty() ? 0 : 1);
+        auto span = [&](const std::vector<int>& a, const std::vector<int>& b) {  // complete linkage
+            double s = 0.0;
+            for (int p : a)
+                for (int q : b)
+                    s = std::max(s, 0.5 * (std::hypot((double)e[p].cu - (double)e[q].cu, (double)e[p].cv - (double)e[q].cv) +
+                                           (double)e[p].rr + (double)e[q].rr));
+            return s;
+        };
+        while (cl.size() > std::max<size_t>(room, 1)) {
+            size_t ba = 0, bb = 1;
+            double bs = INFINITY;
+            for (size_t a = 0; a < cl.size(); ++a)
+                for (size_t b = a + 1; b < cl.size(); ++b) {
+                    const double s = span(cl[a], cl[b]);
+                    if (s < bs) bs = s, ba = a, bb = b;
+                }
+            cl[ba].insert(cl[ba].end(), cl[bb].begin(), cl[bb].end());
+            cl.erase(cl.begin() + (std::ptrdiff_t)bb);
+        }
+        if (!bad.empty()) {
+            if (room == 0 && !cl.empty()) {  // one group in all: the unusable members share it
+                bad.insert(bad.end(), cl[0].begin(), cl[0].end());
+                cl.clear();
+            }
+            cl.insert(cl.begin(), bad);
+        }
+        for (int k = 0; k < SHADOW_GROUPS; ++k) {
+            std::vector<DevShadowCull> m;
+            if ((size_t)k < cl.size())
+                for (int i : cl[(size_t)k]) m.push_back(e[i]), g.mask[k] |= 1u << i;
+            g.grp[k] = shadow_enclose(m.data(), (int)m.size());
+        }
+        const int used = (int)std::min<size_t>(cl.size(), SHADOW_GROUPS);
+        g.uni = shadow_enclose(g.grp, used);
     }
 }
 
@@ -387,7 +548,10 @@ inline SceneLayout scene_build(const rt_sphere* spheres, int n_spheres, const rt
     L.has_shpre = n_spheres < CULL_MIN_SPHERES && n_lights >= 1 && opt.shadow_pre;
     // the direct kernel's mirrored screen boxes, built per view (view_mirror_boxes); RT_MIRROR_BOX=0 turns them off (A/B)
     L.mirror_box = opt.mirror_box;
-    L.bytes = al(L.off_shpre + (L.has_shpre ? sizeof(DevShadowCull) * (size_t)n_lights * (size_t)s_pad : 0)) + 256;
+    // the pre-test's group and union records, one DevShadowGroups per light; RT_SHADOW_GROUPS=0 turns them off (A/B)
+    L.off_shgrp = al(L.off_shpre + (L.has_shpre ? sizeof(DevShadowCull) * (size_t)n_lights * (size_t)s_pad : 0));
+    L.has_shgrp = L.has_shpre && opt.shadow_groups;
+    L.bytes = al(L.off_shgrp + (L.has_shgrp ? sizeof(DevShadowGroups) * (size_t)n_lights : 0)) + 256;
 
     std::vector<unsigned char> blob(L.bytes, 0);
     DevSphere* sph = (DevSphere*)(blob.data() + L.off_sph);
@@ -466,6 +630,9 @@ inline SceneLayout scene_build(const rt_sphere* spheres, int n_spheres, const rt
     if (want_clus) L.n_clus = build_clusters(cull, n_spheres, csize, (DevCluster*)(blob.data() + L.off_clus));
     if (L.has_shcull) build_shadow_cull(li, n_lights, cull, n_spheres, (DevShadowCull*)(blob.data() + L.off_shcull));
     if (L.has_shpre) build_shadow_pre(li, n_lights, cull, n_spheres, s_pad, (DevShadowCull*)(blob.data() + L.off_shpre));
+    if (L.has_shgrp)
+        build_shadow_groups((const DevShadowCull*)(blob.data() + L.off_shpre), n_lights, n_spheres, s_pad,
+                            (DevShadowGroups*)(blob.data() + L.off_shgrp));
     for (int i = 0; i < n_spheres + n_planes; ++i)
         if ((mat[i].flags & MAT_SPEC) && mat[i].pow_kind == POW_GENERIC) L.generic_pow = true;
     L.host_blob = std::move(blob);
