@@ -386,6 +386,40 @@ int rt_render_shutter_bands(rt_ctx* ctx, int width, int height, const rt_camera*
                             size_t frame_stride_bytes, int format, void* hip_stream, int* out_n_bands);
 int rt_render_shutter(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames,
                       int shutter, int32_t* pixels);
+/* Animated scenes: one batch launch, one scene and one camera per frame (ABI 10).
+ *
+ * A scene track is n_frames scene images in device memory.  rt_set_scene_track builds frame f's image from exactly
+ * the arguments rt_set_scene would get for that frame -- spheres[f * n_spheres + i], planes[f * n_planes + j],
+ * lights[f * n_lights + k], ambients[f]; the counts and the recursion limit are those of every frame -- with the
+ * same RT_* switches, and uploads the images back to back.  It replaces an earlier track, after waiting for the
+ * launches that may still read it.  The context's own scene, camera, view cache and progressive run are not
+ * touched: every other render behaves as before.  rt_clear_scene_track frees the track (rt_destroy does too).
+ *
+ * rt_render_anim_bands is rt_render_path_bands with output frame j rendered from track frame first_frame + j and
+ * cameras[j]: bit for bit the frame rt_set_scene(scene first_frame + j), rt_set_camera(cameras[j]) and
+ * rt_render_bands_ex write.  Asynchronous on hip_stream, every format.  rt_render_anim writes whole frames into
+ * host memory through rt_render_path's chunk pipeline.
+ *
+ * Refusals, each before any device call and in this order.  rt_set_scene_track: a NULL context or array
+ * (RT_ERR_INVALID_ARG); n_frames outside 1..RT_MAX_PATH_FRAMES (RT_ERR_INVALID_ARG); counts, limit or lights beyond
+ * rt_set_scene's bounds (its codes); a track above RT_MAX_TRACK_BYTES (RT_ERR_OOM); frames whose cluster counts
+ * differ (RT_ERR_UNSUPPORTED; the builders give equal counts for equal sphere counts).  The renders: a NULL context
+ * or cameras, n_frames outside 1..RT_MAX_PATH_FRAMES (RT_ERR_INVALID_ARG); no track (RT_ERR_NO_SCENE); a bad frame
+ * size, first_frame < 0 or first_frame + n_frames beyond the track (RT_ERR_INVALID_ARG); a context with more than
+ * one worker (RT_ERR_INVALID_ARG); supersampling above 1 (RT_ERR_UNSUPPORTED).  Adaptive and progressive settings
+ * are ignored, as the path calls ignore them.
+ * Frames with a light at the origin, or with a general specular exponent, may be mixed with frames without: the
+ * launch takes the kernels that are exact for every light and every exponent. */
+#define RT_MAX_TRACK_BYTES ((size_t)1 << 30)
+int rt_set_scene_track(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_plane* planes, int n_planes,
+                       const rt_light* lights, int n_lights, const rt_vec3* ambients, int recursion_limit,
+                       int n_frames);
+int rt_clear_scene_track(rt_ctx* ctx);
+int rt_render_anim_bands(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame,
+                         int n_frames, int band_rows, int band_first, int band_step, void* d_out,
+                         size_t frame_stride_bytes, int format, void* hip_stream, int* out_n_bands);
+int rt_render_anim(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame, int n_frames,
+                   int32_t* pixels);
 /* Reassemble the band sets of `world` ranks (band b rendered by rank b % world with
  * band_first = rank, band_step = world), gathered rank after rank at slot_bytes intervals
  * in d_gathered, into the row-major frame d_frame[height][width] -- one launch for all

@@ -192,6 +192,9 @@ struct Device {
     size_t prog_cap = 0;
     hipStream_t prog_stream = nullptr;
     bool prog_touched = false;
+    // rt_set_scene_track: the track's scene images, back to back (worker 0 only: the anim renders are single-worker)
+    void* d_track = nullptr;
+    size_t track_cap = 0;
     float* d_view_tab = nullptr;  // lx[W] then ly[H] (view_tables)
     size_t view_tab_cap = 0;
     int tab_w = -1, tab_h = -1;
@@ -248,6 +251,10 @@ struct rt_ctx {
     bool has_scene = false;
     SceneLayout layout;
     rt_camera cam{};
+    // rt_set_scene_track: the common layout, the stride and the per-frame host records (rt_scene.h SceneTrack, its
+    // image dropped once uploaded); the images live in dev[0].d_track.  Apart from the context's scene.
+    bool has_track = false;
+    SceneTrack track;
     std::string last_error;
     uint64_t frames = 0, pixels = 0, launches = 0;
     uint64_t prim_rays = 0;  // traced pixels (the kernels count only reflect/shadow rays)
@@ -394,10 +401,14 @@ void end_timed(Device& d, bool timed) {
 // The view part of lp for `cam` on a W x VH frame of the context's scene (rt_view.h view_build).  view_params (the
 // context's camera, by value in the kernarg block) and the camera-path calls (one DevView per frame, view_record)
 // both build their views here, so a path frame carries the values a one-camera launch would.
-int view_fill(rt_ctx* ctx, const rt_camera& cam, int W, int VH, LaunchParams& lp) {
-    const int rc = view_build(ctx->layout, cam, W, VH, lp);
+// scene: the records the view is built against -- the context's layout, or a track frame's (trace_anim).
+int view_fill(rt_ctx* ctx, const SceneLayout& scene, const rt_camera& cam, int W, int VH, LaunchParams& lp) {
+    const int rc = view_build(scene, cam, W, VH, lp);
     if (rc != RT_OK) return fail(ctx, rc, "invalid frame size %dx%d", W, VH);
     return RT_OK;
+}
+int view_fill(rt_ctx* ctx, const rt_camera& cam, int W, int VH, LaunchParams& lp) {
+    return view_fill(ctx, ctx->layout, cam, W, VH, lp);
 }
 
 // The view of a W x VH frame (VH: rt_set_view_height, else H), of which a render traces rows [0, H).
@@ -420,9 +431,8 @@ int view_params(rt_ctx* ctx, int W, int H, LaunchParams& lp, int ss = 0) {
     return RT_OK;
 }
 
-void scene_params(const rt_ctx* ctx, const Device& d, LaunchParams& lp) {
-    const SceneLayout& L = ctx->layout;
-    const char* base = (const char*)d.d_scene;
+// The scene part of lp: the tables of the image at `base` laid out as L says, and the scalars derived from it.
+void scene_params(const rt_ctx* ctx, const Device& d, LaunchParams& lp, const SceneLayout& L, const char* base) {
     lp.sph = (const DevSphere*)(base + L.off_sph);
     lp.mat = (const DevMaterial*)(base + L.off_mat);
     lp.pl = (const DevPlane*)(base + L.off_pl);
@@ -440,6 +450,9 @@ void scene_params(const rt_ctx* ctx, const Device& d, LaunchParams& lp) {
     lp.lights_a2_ok = L.lights_a2_ok ? 1 : 0;
     lp.uniform_plane = L.uniform_plane ? 1 : 0;
     lp.counters = ctx->counting ? d.d_counters : nullptr;  // nullptr: the kernels count nothing (rt_set_counting)
+}
+void scene_params(const rt_ctx* ctx, const Device& d, LaunchParams& lp) {
+    scene_params(ctx, d, lp, ctx->layout, (const char*)d.d_scene);
 }
 
 // Per-column / per-row view-plane coordinates of TracePixel (:963-965) on the device (rt_view.h
@@ -613,11 +626,12 @@ struct EncTarget {
 // samples they trace beyond that on the device (CNT_EXTRA_PRIMARY, rt_get_stats).  Nothing but the launch lies between the timing events; a caller that probes the
 // dispatch order brackets the whole call with order_begin / order_end.
 int launch_counted(rt_ctx* ctx, Device& d, hipStream_t stream, const LaunchParams& lp, const char* what, int W, int H,
-                   int band_rows, int first, int step, int nb, int n_frames, int ss) {
+                   int band_rows, int first, int step, int nb, int n_frames, int ss, int generic_pow = -1) {
     hipStream_t saved = d.stream;
     d.stream = stream;
     const bool timed = begin_timed(ctx, d, 0);
-    const int e = launch_trace(lp, ctx->layout.generic_pow, false, stream);
+    // (generic_pow: the launch's scene is not the context's -- a scene track's OR over its frames)
+    const int e = launch_trace(lp, generic_pow < 0 ? ctx->layout.generic_pow : generic_pow != 0, false, stream);
     end_timed(d, timed);
     d.stream = saved;
     if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString((hipError_t)e));
@@ -1094,6 +1108,7 @@ void rt_destroy(rt_ctx* ctx) {
         if (d.copy_stream) (void)hipStreamDestroy(d.copy_stream);
         if (d.comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(d.comm);
         if (d.d_scene) (void)hipFree(d.d_scene);
+        if (d.d_track) (void)hipFree(d.d_track);
         if (d.d_frame) (void)hipFree(d.d_frame);
         if (d.d_bands) (void)hipFree(d.d_bands);
         if (d.d_gather) (void)hipFree(d.d_gather);
@@ -1112,21 +1127,9 @@ void rt_destroy(rt_ctx* ctx) {
     delete ctx;
 }
 
-int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_plane* planes, int n_planes,
-                 const rt_light* lights, int n_lights, rt_vec3 ambient, int recursion_limit) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "NULL context");
-    if (n_spheres < 0 || n_planes < 0 || n_lights < 0 || (n_spheres && !spheres) || (n_planes && !planes) ||
-        (n_lights && !lights))
-        return fail(ctx, RT_ERR_INVALID_ARG, "rt_set_scene: bad primitive arrays");
-    if (recursion_limit < 0) return fail(ctx, RT_ERR_INVALID_ARG, "recursion_limit must be >= 0");
-    if (n_lights > RT_MAX_LIGHTS)
-        return fail(ctx, RT_ERR_UNSUPPORTED, "n_lights %d > RT_MAX_LIGHTS (%d)", n_lights, RT_MAX_LIGHTS);
-    if (recursion_limit > RT_MAX_RECURSION_LIMIT)
-        return fail(ctx, RT_ERR_UNSUPPORTED, "recursion_limit %d > RT_MAX_RECURSION_LIMIT (%d)", recursion_limit,
-                    RT_MAX_RECURSION_LIMIT);
-
-    // the switches of rt_scene.h SceneOptions (A/B and fallback tests): RT_<NAME>=0 turns a table off,
-    // RT_TRACE_CLUSTERS=0 the clusters, =2..16 sets the cluster size
+// The switches of rt_scene.h SceneOptions (A/B and fallback tests) as rt_set_scene and rt_set_scene_track read them:
+// RT_<NAME>=0 turns a table off, RT_TRACE_CLUSTERS=0 the clusters, =2..16 sets the cluster size.
+static SceneOptions scene_options_from_env() {
     auto off = [](const char* name) {
         const char* v = std::getenv(name);
         return v && std::strcmp(v, "0") == 0;
@@ -1140,6 +1143,29 @@ int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_
     opt.dark_skip = !off("RT_DARK_SKIP");
     opt.prim_foot = !off("RT_PRIM_FOOT");
     opt.uniform_plane = !off("RT_UNIFORM_PLANE");
+    return opt;
+}
+
+// The argument checks rt_set_scene and rt_set_scene_track (per frame: the same counts) share.
+static int check_scene_args(rt_ctx* ctx, const char* who, const void* spheres, int n_spheres, const void* planes, int n_planes,
+                            const void* lights, int n_lights, int recursion_limit) {
+    if (n_spheres < 0 || n_planes < 0 || n_lights < 0 || (n_spheres && !spheres) || (n_planes && !planes) ||
+        (n_lights && !lights))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: bad primitive arrays", who);
+    if (recursion_limit < 0) return fail(ctx, RT_ERR_INVALID_ARG, "recursion_limit must be >= 0");
+    if (n_lights > RT_MAX_LIGHTS)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "n_lights %d > RT_MAX_LIGHTS (%d)", n_lights, RT_MAX_LIGHTS);
+    if (recursion_limit > RT_MAX_RECURSION_LIMIT)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "recursion_limit %d > RT_MAX_RECURSION_LIMIT (%d)", recursion_limit,
+                    RT_MAX_RECURSION_LIMIT);
+    return RT_OK;
+}
+
+int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_plane* planes, int n_planes,
+                 const rt_light* lights, int n_lights, rt_vec3 ambient, int recursion_limit) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "NULL context");
+    RT_TRY(check_scene_args(ctx, "rt_set_scene", spheres, n_spheres, planes, n_planes, lights, n_lights, recursion_limit));
+    const SceneOptions opt = scene_options_from_env();
     SceneLayout L = scene_build(spheres, n_spheres, planes, n_planes, lights, n_lights, ambient, recursion_limit, opt);
     for (Device& d : ctx->dev) {
         DeviceGuard guard(d.id);
@@ -1154,6 +1180,64 @@ int rt_set_scene(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_
     ctx->has_scene = true;
     ctx->view_ok = false;
     ctx->scene_gen++;
+    return RT_OK;
+}
+
+// The frames of a track are built by a thread pool (rt_scene.h track_build): a frame's build costs more than its
+// trace in both families -- about 1 ms for 8 spheres and 2 lights (the shadow pre-test's group records) against a
+// 20 us trace at 1080p, about 4 ms for 64 spheres and 4 lights (the shadow grids) against 0.3 ms at 4K.
+// min(16, n_frames) threads, never sized by the machine; the image does not depend on the thread count.
+static int track_threads(int n_frames) { return std::min(16, n_frames); }
+
+int rt_set_scene_track(rt_ctx* ctx, const rt_sphere* spheres, int n_spheres, const rt_plane* planes, int n_planes,
+                       const rt_light* lights, int n_lights, const rt_vec3* ambients, int recursion_limit, int n_frames) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "NULL context");
+    if (!ambients) return fail(ctx, RT_ERR_INVALID_ARG, "rt_set_scene_track: NULL ambients");
+    if ((n_spheres > 0 && !spheres) || (n_planes > 0 && !planes) || (n_lights > 0 && !lights))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_set_scene_track: bad primitive arrays");
+    if (n_frames <= 0 || n_frames > RT_MAX_PATH_FRAMES)
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_set_scene_track: a frame count outside 1..%d", RT_MAX_PATH_FRAMES);
+    RT_TRY(check_scene_args(ctx, "rt_set_scene_track", spheres, n_spheres, planes, n_planes, lights, n_lights, recursion_limit));
+    const SceneOptions opt = scene_options_from_env();
+    const size_t frame_bytes = track_frame_bytes(n_spheres, n_planes, n_lights, opt);
+    if (frame_bytes > RT_MAX_TRACK_BYTES / (size_t)n_frames)
+        return fail(ctx, RT_ERR_OOM, "rt_set_scene_track: %d frames of %zu bytes exceed RT_MAX_TRACK_BYTES (%zu)", n_frames,
+                    frame_bytes, (size_t)RT_MAX_TRACK_BYTES);
+    SceneTrack T;
+    const int tb = track_build(spheres, n_spheres, planes, n_planes, lights, n_lights, ambients, recursion_limit, n_frames, opt,
+                               track_threads(n_frames), &T);
+    if (tb == TRACK_CLUSTERS)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_set_scene_track: the frames' cluster counts differ");
+    if (tb != TRACK_OK || T.stride % 256 != 0)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_set_scene_track: the frames' scene layouts differ");
+    if (!ctx->dev.empty()) {
+        Device& d = ctx->dev[0];
+        DeviceGuard guard(d.id);
+        // launches in flight on any stream may read the track being replaced
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        ctx->has_track = false;
+        RT_TRY(grow(ctx, &d.d_track, &d.track_cap, T.image.size()));
+        HIP_TRY(ctx, hipMemcpy(d.d_track, T.image.data(), T.image.size(), hipMemcpyHostToDevice));
+    }
+    std::vector<unsigned char>().swap(T.image);
+    ctx->track = std::move(T);
+    ctx->has_track = true;
+    return RT_OK;
+}
+
+int rt_clear_scene_track(rt_ctx* ctx) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "NULL context");
+    if (!ctx->dev.empty()) {
+        Device& d = ctx->dev[0];
+        DeviceGuard guard(d.id);
+        if (d.d_track) {
+            HIP_TRY(ctx, hipDeviceSynchronize());  // (launches that still read it)
+            (void)hipFree(d.d_track);
+        }
+        d.d_track = nullptr, d.track_cap = 0;
+    }
+    ctx->has_track = false;
+    ctx->track = SceneTrack{};
     return RT_OK;
 }
 
@@ -1783,8 +1867,13 @@ int view_table_fill(rt_ctx* ctx, const rt_camera* cams, int n_views, int W, int 
 // With a shutter (rt_render_shutter_bands, t = log2 of it > 0) the table holds n_frames << t records, sub-frame s
 // of output frame f at f << t | s = cams' own order, and the launch -- still n_frames frames in grid z -- averages
 // each frame's 1 << t records in the kernel (LaunchParams::shutter_log2); t = 0 is the path launch itself.
-int trace_path(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const rt_camera* cams, int n_frames, int t,
-               int band_rows, int first, int step, void* out, size_t frame_bytes, int fmt) {
+// With a scene track (trace_anim: track != nullptr, t = 0) frame j of the launch also has its own scene, track frame
+// first_frame + j: record j is built against that frame's spheres and planes -- the primary constants, the screen
+// boxes and the mirrored boxes all depend on them -- the block's scene pointers are set to that first frame's image,
+// and grid z steps through the images by LaunchParams::scene_stride (the ANIM kernels).
+int trace_views(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const rt_camera* cams, int n_frames, int t,
+                int band_rows, int first, int step, void* out, size_t frame_bytes, int fmt, const SceneTrack* track,
+                int first_frame) {
     const int n_views = n_frames << t;  // (the callers bound it by RT_MAX_PATH_FRAMES)
     const int VH = ctx->view_height > 0 ? ctx->view_height : H;
     if (H > VH) return fail(ctx, RT_ERR_INVALID_ARG, "frame height %d above the view height %d", H, ctx->view_height);
@@ -1812,10 +1901,23 @@ int trace_path(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const r
     }
     LaunchParams lp;
     std::memset(&lp, 0, sizeof lp);
-    int rc = view_table_fill(ctx, cams, n_views, W, VH, lp, ps.h_views);
+    int rc = RT_OK;
+    if (track) {
+        for (int j = 0; j < n_views && rc == RT_OK; ++j) {
+            rc = view_fill(ctx, track->frames[(size_t)(first_frame + j)], cams[j], W, VH, lp);
+            if (rc == RT_OK) view_record(lp, ps.h_views[j]);
+        }
+    } else {
+        rc = view_table_fill(ctx, cams, n_views, W, VH, lp, ps.h_views);
+    }
     if (rc != RT_OK) return rc;
     lp.H = H;  // the rows traced; pw, ph, nearc and W are the same for every camera (lxt / lyt: view_tables)
-    scene_params(ctx, d, lp);
+    if (track) {
+        scene_params(ctx, d, lp, track->common, (const char*)d.d_track + (size_t)first_frame * track->stride);
+        lp.scene_stride = track->stride;
+    } else {
+        scene_params(ctx, d, lp);
+    }
     rc = view_tables(ctx, d, lp);
     if (rc != RT_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ps.d_views, ps.h_views, (size_t)n_views * sizeof(DevView), hipMemcpyHostToDevice, stream));
@@ -1827,11 +1929,22 @@ int trace_path(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const r
     lp.out_fmt = fmt;
     lp.n_frames = n_frames;
     lp.out_frame_bytes = frame_bytes;
-    rc = launch_counted(ctx, d, stream, lp, "path", W, H, band_rows, first, step, nb, n_views, 0);  // (primary rays: every sub-frame's)
+    rc = launch_counted(ctx, d, stream, lp, track ? "anim" : "path", W, H, band_rows, first, step, nb, n_views, 0,
+                        track ? (track->common.generic_pow ? 1 : 0) : -1);  // (primary rays: every sub-frame's)
     if (rc != RT_OK) return rc;
     HIP_TRY(ctx, hipEventRecord(ps.done, stream));
     ps.busy = true;
     return RT_OK;
+}
+int trace_path(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const rt_camera* cams, int n_frames, int t,
+               int band_rows, int first, int step, void* out, size_t frame_bytes, int fmt) {
+    return trace_views(ctx, d, stream, W, H, cams, n_frames, t, band_rows, first, step, out, frame_bytes, fmt, nullptr, 0);
+}
+// n_frames frames from track frame first_frame on, frame j with cams[j] (check_anim bounds them).
+int trace_anim(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const rt_camera* cams, int first_frame, int n_frames,
+               int band_rows, int first, int step, void* out, size_t frame_bytes, int fmt) {
+    return trace_views(ctx, d, stream, W, H, cams, n_frames, 0, band_rows, first, step, out, frame_bytes, fmt, &ctx->track,
+                       first_frame);
 }
 
 int check_path(rt_ctx* ctx, const char* who, int W, int H, const rt_camera* cams, int n_frames) {
@@ -1840,6 +1953,22 @@ int check_path(rt_ctx* ctx, const char* who, int W, int H, const rt_camera* cams
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: NULL cameras or a frame count outside 1..%d", who, RT_MAX_PATH_FRAMES);
     int rc = check_ctx(ctx, W, H, false);
     if (rc != RT_OK) return rc;
+    if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s needs a single-GPU context", who);
+    if (ctx->ss_log2 > 0) return fail(ctx, RT_ERR_UNSUPPORTED, "%s does not supersample", who);
+    return RT_OK;
+}
+
+// check_path for the scene-track renders: the track stands where the scene does, then the frame range.
+int check_anim(rt_ctx* ctx, const char* who, int W, int H, const rt_camera* cams, int first_frame, int n_frames) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "NULL context");
+    if (!cams || n_frames <= 0 || n_frames > RT_MAX_PATH_FRAMES)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: NULL cameras or a frame count outside 1..%d", who, RT_MAX_PATH_FRAMES);
+    if (!ctx->has_track) return fail(ctx, RT_ERR_NO_SCENE, "%s: rt_set_scene_track has not been called", who);
+    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31) - 1)
+        return fail(ctx, RT_ERR_INVALID_ARG, "invalid frame size %dx%d", W, H);
+    if (first_frame < 0 || (long long)first_frame + n_frames > ctx->track.n_frames)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: frames %d..%lld outside the track's %d", who, first_frame,
+                    (long long)first_frame + n_frames - 1, ctx->track.n_frames);
     if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s needs a single-GPU context", who);
     if (ctx->ss_log2 > 0) return fail(ctx, RT_ERR_UNSUPPORTED, "%s does not supersample", who);
     return RT_OK;
@@ -1860,18 +1989,23 @@ int check_shutter(rt_ctx* ctx, const char* who, int n_frames, int shutter, int* 
 }
 
 // rt_render_path_bands and rt_render_shutter_bands (t = log2 of the shutter) after their argument checks.
+// first_frame >= 0: rt_render_anim_bands, the frames of the context's scene track from that one on.
 int path_bands(rt_ctx* ctx, const char* who, int width, int height, const rt_camera* cameras, int n_frames, int t,
                int band_rows, int band_first, int band_step, void* d_out, size_t frame_stride_bytes, int format,
-               void* hip_stream, int* out_n_bands) {
-    RT_TRY(check_path(ctx, who, width, height, cameras, n_frames));
+               void* hip_stream, int* out_n_bands, int first_frame = -1) {
+    const bool anim = first_frame != -1;
+    RT_TRY(anim ? check_anim(ctx, who, width, height, cameras, first_frame, n_frames)
+                : check_path(ctx, who, width, height, cameras, n_frames));
     RT_TRY(check_band_args(ctx, who, band_rows, band_first, band_step, d_out, format));
     const int nb = bands_of(height, band_rows, band_first, band_step);
     if (n_frames > 1 && frame_stride_bytes < band_output_bytes(width, height, nb, band_rows, format))
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: frame stride smaller than a frame's output", who);
     Device& d = ctx->dev[0];
     DeviceGuard guard(d.id);
-    const int rc = trace_path(ctx, d, (hipStream_t)hip_stream, width, height, cameras, n_frames, t, band_rows, band_first,
-                              band_step, d_out, frame_stride_bytes, format);
+    const int rc = anim ? trace_anim(ctx, d, (hipStream_t)hip_stream, width, height, cameras, first_frame, n_frames, band_rows,
+                                     band_first, band_step, d_out, frame_stride_bytes, format)
+                        : trace_path(ctx, d, (hipStream_t)hip_stream, width, height, cameras, n_frames, t, band_rows, band_first,
+                                     band_step, d_out, frame_stride_bytes, format);
     if (out_n_bands) *out_n_bands = nb;
     if (rc == RT_OK) ctx->pixels += (uint64_t)nb * band_rows * width * (uint64_t)n_frames;
     return rc;
@@ -1902,8 +2036,10 @@ int rt_render_shutter_bands(rt_ctx* ctx, int width, int height, const rt_camera*
 // a chunk's launch takes its chunk << t cameras).
 namespace {
 int path_frames(rt_ctx* ctx, const char* who, int width, int height, const rt_camera* cameras, int n_frames, int t,
-                int32_t* pixels) {
-    int rc = check_path(ctx, who, width, height, cameras, n_frames);
+                int32_t* pixels, int first_frame = -1) {
+    const bool anim = first_frame != -1;  // rt_render_anim: the scene track's frames from that one on
+    int rc = anim ? check_anim(ctx, who, width, height, cameras, first_frame, n_frames)
+                  : check_path(ctx, who, width, height, cameras, n_frames);
     if (rc != RT_OK) return rc;
     if (!pixels) return fail(ctx, RT_ERR_INVALID_ARG, "NULL pixels");
     RT_TRY(wait_pending_async(ctx));
@@ -1929,8 +2065,10 @@ int path_frames(rt_ctx* ctx, const char* who, int width, int height, const rt_ca
     for (int c = 0; c < n_chunks; ++c) {
         const int f0 = c * chunk, nf = std::min(chunk, n_frames - f0), b = c & 1;
         if (c >= 2 && !hip_ok(hipStreamWaitEvent(d.stream, copied[b], 0), "hipStreamWaitEvent")) break;
-        rc = trace_path(ctx, d, d.stream, width, height, cameras + ((size_t)f0 << t), nf, t, height, 0, 1, d.d_path[b],
-                        frame_bytes, RT_BANDS_INT32);
+        rc = anim ? trace_anim(ctx, d, d.stream, width, height, cameras + f0, first_frame + f0, nf, height, 0, 1, d.d_path[b],
+                               frame_bytes, RT_BANDS_INT32)
+                  : trace_path(ctx, d, d.stream, width, height, cameras + ((size_t)f0 << t), nf, t, height, 0, 1, d.d_path[b],
+                               frame_bytes, RT_BANDS_INT32);
         if (rc != RT_OK) break;
         // (into a range that is not registered the runtime stages this copy and the call returns only when it is
         // done: chunk c + 1 is then traced after the copy of chunk c, not under it)
@@ -1959,6 +2097,20 @@ int rt_render_shutter(rt_ctx* ctx, int width, int height, const rt_camera* camer
     int t = 0;
     RT_TRY(check_shutter(ctx, "rt_render_shutter", n_frames, shutter, &t));
     return path_frames(ctx, t ? "rt_render_shutter" : "rt_render_path", width, height, cameras, n_frames, t, pixels);
+}
+
+int rt_render_anim_bands(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame, int n_frames,
+                         int band_rows, int band_first, int band_step, void* d_out, size_t frame_stride_bytes, int format,
+                         void* hip_stream, int* out_n_bands) {
+    if (first_frame == -1) first_frame = INT_MIN;  // (-1 marks the path calls inside path_bands: refused like any negative)
+    return path_bands(ctx, "rt_render_anim_bands", width, height, cameras, n_frames, 0, band_rows, band_first, band_step,
+                      d_out, frame_stride_bytes, format, hip_stream, out_n_bands, first_frame);
+}
+
+int rt_render_anim(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame, int n_frames,
+                   int32_t* pixels) {
+    if (first_frame == -1) first_frame = INT_MIN;
+    return path_frames(ctx, "rt_render_anim", width, height, cameras, n_frames, 0, pixels, first_frame);
 }
 
 // Double-buffered Tick() on one in-order stream per worker.  Frame k's band set is traced into device

@@ -205,8 +205,12 @@ __device__ __forceinline__ void encode_tile_fused(const LaunchParams& p, uint32_
 // ViewOf as a member, from the kernel body's loop counter through every function that builds one.  It is made of
 // blockIdx.z, a kernarg and a wave-uniform loop counter only, so it lives in an SGPR and the reads stay scalar
 // loads.  The other views never read `rec` (it is a dead constant 0 there: their code is what it was).
-constexpr int VIEW_ARGS = 0, VIEW_PATH = 1, VIEW_SHUTTER = 2;
-constexpr int view_of(unsigned V) { return (V & VF_SHUTTER) ? VIEW_SHUTTER : (V & VF_PATH) ? VIEW_PATH : VIEW_ARGS; }
+// ANIM (scene tracks, rt_render_anim_bands): PATH's view -- every ViewOf member reads the frame's record exactly as
+// VIEW_PATH does -- in a launch whose frames also have their own scene image (SceneOf below).
+constexpr int VIEW_ARGS = 0, VIEW_PATH = 1, VIEW_SHUTTER = 2, VIEW_ANIM = 3;
+constexpr int view_of(unsigned V) {
+    return (V & VF_SHUTTER) ? VIEW_SHUTTER : (V & VF_ANIM) ? VIEW_ANIM : (V & VF_PATH) ? VIEW_PATH : VIEW_ARGS;
+}
 template <int PATH>
 struct ViewOf {
     const LaunchParams& p;
@@ -264,6 +268,42 @@ struct ViewOf {
     }
 };
 
+// The scene of the wave's frame: the 12 scene tables of LaunchParams, read through this accessor everywhere.  ANIM
+// (a scene track: one scene image per grid z, LaunchParams::scene_stride bytes apart): frame z's table is the
+// launch's pointer + z * scene_stride.  blockIdx.z and the stride are wave-uniform, so the address is scalar
+// arithmetic and the reads stay the scalar loads they are in every other instantiation.  The tables a scene may lack
+// (shcull, shpre, shg, shgrid, shslab, clus, shgrp) stay null when they are null in the block; sph, mat, pl, li and
+// scull are set by every launch (rt_api.cpp scene_params).  Any other view kind: the pointer itself, a compile-time
+// identity -- the code of those instantiations is what it was (static members: an accessor object's temporary inside
+// a short-circuit chain moved the class-0 bundle kernels' SGPR spills by up to 15).  The kind travels as the PATH
+// parameter that ViewOf takes; the functions that read the scene have no default for it, so no call can fall back to
+// the launch's image.
+template <int PATH>
+struct SceneOf {
+    template <bool NULLABLE, typename T>
+    static __device__ __forceinline__ const T* at(const LaunchParams& p, const T* q) {
+        if constexpr (PATH == VIEW_ANIM) {
+            const T* z = (const T*)((const char*)q + (size_t)blockIdx.z * (size_t)p.scene_stride);
+            if constexpr (NULLABLE) return q == nullptr ? nullptr : z;
+            else return z;
+        } else {
+            return q;
+        }
+    }
+    static __device__ __forceinline__ const DevSphere* sph(const LaunchParams& p) { return at<false>(p, p.sph); }
+    static __device__ __forceinline__ const DevMaterial* mat(const LaunchParams& p) { return at<false>(p, p.mat); }
+    static __device__ __forceinline__ const DevPlane* pl(const LaunchParams& p) { return at<false>(p, p.pl); }
+    static __device__ __forceinline__ const DevLight* li(const LaunchParams& p) { return at<false>(p, p.li); }
+    static __device__ __forceinline__ const DevSphereCull* scull(const LaunchParams& p) { return at<false>(p, p.scull); }
+    static __device__ __forceinline__ const DevShadowCull* shcull(const LaunchParams& p) { return at<true>(p, p.shcull); }
+    static __device__ __forceinline__ const DevShadowCull* shpre(const LaunchParams& p) { return at<true>(p, p.shpre); }
+    static __device__ __forceinline__ const DevShadowGrid* shg(const LaunchParams& p) { return at<true>(p, p.shg); }
+    static __device__ __forceinline__ const unsigned long long* shgrid(const LaunchParams& p) { return at<true>(p, p.shgrid); }
+    static __device__ __forceinline__ const unsigned long long* shslab(const LaunchParams& p) { return at<true>(p, p.shslab); }
+    static __device__ __forceinline__ const DevCluster* clus(const LaunchParams& p) { return at<true>(p, p.clus); }
+    static __device__ __forceinline__ const DevShadowGroups* shgrp(const LaunchParams& p) { return at<true>(p, p.shgrp); }
+};
+
 // Deep-recursion stack (recursion limits >= 8): whole records {hit point, t} and {incoming
 // direction, primitive code}, dynamically indexed, in scratch.
 template <int K>
@@ -277,14 +317,14 @@ struct ScratchStack {
         b[n] = y;
         ++n;
     }
-    template <int PATH = VIEW_ARGS>
+    template <int PATH>
     __device__ __forceinline__ void pop(const LaunchParams&, float4& x, float4& y, int = 0) {
         --n;
         x = a[n];
         y = b[n];
     }
     // the level-0 record (n >= 1), as pop hands it out; the stack is left as it is
-    template <int PATH = VIEW_ARGS>
+    template <int PATH>
     __device__ __forceinline__ void level0(const LaunchParams&, float4& x, float4& y, int = 0) {
         x = a[0];
         y = b[0];
@@ -296,14 +336,15 @@ struct ScratchStack {
 // CalculateReflectionRay :718-720): hit point of segment (o, d) at t, then the reflected
 // segment.  The walks and the compact stacks' re-walk share it, so the re-walk reproduces
 // every hit point and direction bit for bit.
+template <int PATH>
 __device__ __forceinline__ f3 reflect_at(const LaunchParams& p, f3 o, f3& d, float t, int code) {
     const f3 hp = add(o, scale(d, t));
     f3 normal;
     if (code >= 0) {
-        const DevSphere& s = p.sph[code];
+        const DevSphere& s = SceneOf<PATH>::sph(p)[code];
         normal = normalize(sub(hp, mk(s.cx, s.cy, s.cz)));
     } else {
-        const DevPlane& pl = p.pl[~code];
+        const DevPlane& pl = SceneOf<PATH>::pl(p)[~code];
         normal = mk(pl.nx, pl.ny, pl.nz);
     }
     d = sub(d, scale(normal, 2.0f * dot(d, normal)));
@@ -330,7 +371,7 @@ struct LdsStack {
         lv[n * WG_THREADS + (threadIdx.x & 63)] = make_float2(x.w, y.w);
         ++n;
     }
-    template <int PATH = VIEW_ARGS>
+    template <int PATH>
     __device__ __forceinline__ void pop(const LaunchParams& p, float4& x, float4& y, int rec = 0) {
         --n;
         f3 o = ViewOf<PATH>{p, rec}.cam();
@@ -341,7 +382,7 @@ struct LdsStack {
             if (__builtin_amdgcn_ballot_w64(go) == 0) break;
             if (go) {
                 const float2 tc = lv[j * WG_THREADS + (threadIdx.x & 63)];
-                o = reflect_at(p, o, d, tc.x, __float_as_int(tc.y));
+                o = reflect_at<PATH>(p, o, d, tc.x, __float_as_int(tc.y));
             }
         }
         const float2 tk = lv[n * WG_THREADS + (threadIdx.x & 63)];
@@ -351,7 +392,7 @@ struct LdsStack {
     }
     // the level-0 record (n >= 1) without a re-walk: pop's own operations at n = 0 -- the camera, the primary
     // direction, hp = cam + d t -- and no loop; the stack is left as it is
-    template <int PATH = VIEW_ARGS>
+    template <int PATH>
     __device__ __forceinline__ void level0(const LaunchParams& p, float4& x, float4& y, int rec = 0) {
         const f3 o = ViewOf<PATH>{p, rec}.cam();
         const f3 d = mk(dv[(threadIdx.x & 63)], dv[WG_THREADS + (threadIdx.x & 63)], dv[2 * WG_THREADS + (threadIdx.x & 63)]);
@@ -601,35 +642,35 @@ __device__ __forceinline__ void for_sphere_pairs(const LaunchParams& p, F body) 
 // same spheres are tested exactly, in the same ascending order: pixels, ray counts and the tallies are unchanged.
 // The group level on top (a member mask from the three group records, pairs outside it skipped) gained no more on C3
 // and cost the scan without records 0.3 us in spilled SGPRs and serial scalar loads: profiles/ab/r15_shadow_groups.txt.
-template <bool A2OK, bool GROUPS, typename T>
+template <bool A2OK, bool GROUPS, int PATH, typename T>
 __device__ __forceinline__ bool shadow_scan(const LaunchParams& p, f3 hp, const DevLight& l, int li, T& tl) {
     int blk = 0;
-    if (A2OK && p.shpre != nullptr) {  // wave-uniform
+    if (A2OK && SceneOf<PATH>::shpre(p) != nullptr) {  // wave-uniform
         const ShadowPreLane q = shadow_pre_lane(hp.x, hp.y, hp.z, l);
         if constexpr (GROUPS) {
             // wave-uniform: no lane keeps the union of the light's discs -- not blocked, no sphere visited
-            if (p.shgrp != nullptr &&
-                __builtin_amdgcn_ballot_w64(shadow_pre_keep(shadow_pre_widen(q, SHADOW_UNION_WIDEN), p.shgrp[li].uni)) == 0)
+            if (SceneOf<PATH>::shgrp(p) != nullptr &&
+                __builtin_amdgcn_ballot_w64(shadow_pre_keep(shadow_pre_widen(q, SHADOW_UNION_WIDEN), SceneOf<PATH>::shgrp(p)[li].uni)) == 0)
                 return false;
         }
-        const DevShadowCull* e = p.shpre + (size_t)li * (size_t)(p.S + (p.S & 1));
+        const DevShadowCull* e = SceneOf<PATH>::shpre(p) + (size_t)li * (size_t)(p.S + (p.S & 1));
         for_sphere_pairs<T>(p, [&](int i) {
             const DevShadowCull e0 = e[i], e1 = e[i + 1];
             const bool k0 = shadow_pre_keep(q, e0), k1 = shadow_pre_keep(q, e1);
             if (__builtin_amdgcn_ballot_w64(k0) != 0) {  // wave-uniform: some lane's ray may be blocked
                 tl.shadow_sphere(blk == 0);
-                blk = shadow_blocked<A2OK>(hp, l, false, p.sph[i]) ? 1 : blk;
+                blk = shadow_blocked<A2OK>(hp, l, false, SceneOf<PATH>::sph(p)[i]) ? 1 : blk;
             }
             if (__builtin_amdgcn_ballot_w64(k1) != 0) {
                 tl.shadow_sphere(blk == 0);
-                blk = shadow_blocked<A2OK>(hp, l, false, p.sph[i + 1]) ? 1 : blk;
+                blk = shadow_blocked<A2OK>(hp, l, false, SceneOf<PATH>::sph(p)[i + 1]) ? 1 : blk;
             }
         });
         return blk != 0;
     }
     for_sphere_pairs<T>(p, [&](int i) {
         tl.shadow_sphere(blk == 0);
-        const DevSphere s0 = p.sph[i], s1 = p.sph[i + 1];
+        const DevSphere s0 = SceneOf<PATH>::sph(p)[i], s1 = SceneOf<PATH>::sph(p)[i + 1];
         blk = shadow_blocked<A2OK>(hp, l, false, s0) ? 1 : blk;
         tl.shadow_sphere((blk == 0) & (i + 1 < p.S));
         blk = shadow_blocked<A2OK>(hp, l, false, s1) ? 1 : blk;
@@ -637,20 +678,20 @@ __device__ __forceinline__ bool shadow_scan(const LaunchParams& p, f3 hp, const 
     return blk != 0;
 }
 
-template <bool GPOW, bool GROUPS = false, typename T>
+template <bool GPOW, bool GROUPS, int PATH, typename T>
 __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere, int prim, f3 hp, f3 d, float t, f3 sec,
                                            unsigned* n_shadow, T& tl) {
-    const DevMaterial& m = p.mat[is_sphere ? prim : p.S + prim];
+    const DevMaterial& m = SceneOf<PATH>::mat(p)[is_sphere ? prim : p.S + prim];
     const uint32_t flags = m.flags;
     f3 normal;
     float tile = 1.0f;
     // A plane hit on a dark square whose light terms are provably +0 (rt_dark.h): the light loop is skipped
     bool dark = false;
     if (is_sphere) {
-        const DevSphere& s = p.sph[prim];
+        const DevSphere& s = SceneOf<PATH>::sph(p)[prim];
         normal = normalize(sub(hp, mk(s.cx, s.cy, s.cz)));  // SpherePhongShading :706
     } else {
-        const DevPlane& pl = p.pl[prim];
+        const DevPlane& pl = SceneOf<PATH>::pl(p)[prim];
         normal = mk(pl.nx, pl.ny, pl.nz);
         // checkerboard, :766-770: ((int)u + (int)v) & 1, unchecked int add
         const float u = dot(mk(pl.e1x, pl.e1y, pl.e1z), hp);
@@ -670,7 +711,7 @@ __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere
         const uint32_t pk = m.pow_kind;
         const float pn = m.n;
         for (int li = 0; li < p.L; ++li) {
-            const DevLight& l = p.li[li];
+            const DevLight& l = SceneOf<PATH>::li(p)[li];
             const bool l_ok = l.a2 > 0.0f && l.a2 < __builtin_inff();  // wave-uniform
             // ShapePhongShading, :665-695 (first: it decides whether the shadow test matters)
             const f3 ldir = normalize(sub(mk(l.px, l.py, l.pz), hp));
@@ -685,7 +726,7 @@ __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere
             bool blocked = false;
             if (shadow_matters(ph, l.intensity, att)) {
                 tl.shadow(true);
-                blocked = l_ok ? shadow_scan<true, GROUPS>(p, hp, l, li, tl) : shadow_scan<false, false>(p, hp, l, li, tl);
+                blocked = l_ok ? shadow_scan<true, GROUPS, PATH>(p, hp, l, li, tl) : shadow_scan<false, false, PATH>(p, hp, l, li, tl);
             }
             const float inten = blocked ? 0.0f : l.intensity;
             const float ia = inten * att;
@@ -708,10 +749,10 @@ __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere
 // records arrive by scalar loads, and the flag tests and the exponent switch are scalar branches.  The dark-square
 // test, the light loop, the shadow scans, the clamps and the counts stay per lane.  Converged call on the wave's
 // level-0 lanes.
-template <typename T>
+template <int PATH, typename T>
 __device__ __forceinline__ f3 shade_plane_uniform(const LaunchParams& p, int plane, f3 hp, f3 d, float t, f3 sec,
                                                   unsigned* n_shadow, T& tl) {
-    return shade_direct<false, RT_SHADOW_GROUPS != 0>(p, false, plane, hp, d, t, sec, n_shadow, tl);
+    return shade_direct<false, RT_SHADOW_GROUPS != 0, PATH>(p, false, plane, hp, d, t, sec, n_shadow, tl);
 }
 
 // Candidate spheres of a wave's primary rays: those whose per-frame screen box (view_params)
@@ -810,7 +851,7 @@ __device__ __forceinline__ TilePixel sample_pixel(const LaunchParams& p, int til
 // (mirror_box_select; all ones: every sphere) and a pair runs only when one of its bits is set -- a skipped
 // sphere's test yields t <= 0 or NaN on every active lane, which take_secondary rejects, and the kept ones are
 // still visited in ascending index.
-template <bool PRIMARY, bool A2OK, bool GATED = false, int PATH = VIEW_ARGS, typename T>
+template <bool PRIMARY, bool A2OK, bool GATED, int PATH, typename T>
 __device__ __forceinline__ void nearest_spheres(const LaunchParams& p, f3 o, f3 d, float a2, float a4, bool a2_ok,
                                                 unsigned long long pmask, float& best_s, int& win_s, T& tl, int rec = 0) {
     if (PRIMARY && ViewOf<PATH>{p, rec}.prim_const()) {
@@ -834,7 +875,7 @@ __device__ __forceinline__ void nearest_spheres(const LaunchParams& p, f3 o, f3 
             }
             tl.sphere(true);
             tl.sphere(i + 1 < p.S);
-            const DevSphere s0 = p.sph[i], s1 = p.sph[i + 1];
+            const DevSphere s0 = SceneOf<PATH>::sph(p)[i], s1 = SceneOf<PATH>::sph(p)[i + 1];
             const float t0 = sphere_t<A2OK>(o, d, a2, a4, a2_ok, s0);
             const float t1 = sphere_t<A2OK>(o, d, a2, a4, a2_ok, s1);
             if (PRIMARY) {
@@ -848,7 +889,7 @@ __device__ __forceinline__ void nearest_spheres(const LaunchParams& p, f3 o, f3 
     }
 }
 
-template <bool PRIMARY, bool GATED = false, int PATH = VIEW_ARGS, typename T>
+template <bool PRIMARY, bool GATED, int PATH, typename T>
 __device__ __forceinline__ Hit nearest_direct(const LaunchParams& p, f3 o, f3 d, T& tl, unsigned long long pmask = 0,
                                               int rec = 0) {
     const float a = dot(d, d);
@@ -864,7 +905,7 @@ __device__ __forceinline__ Hit nearest_direct(const LaunchParams& p, f3 o, f3 d,
     int win_p = -1;
     for (int i = 0; i < p.P; ++i) {
         tl.plane(true);
-        plane_take(o, d, p.pl[i], i, best_p, win_p);  // t > 0 && t < best (:985-991, :819-821)
+        plane_take(o, d, SceneOf<PATH>::pl(p)[i], i, best_p, win_p);  // t > 0 && t < best (:985-991, :819-821)
     }
     if (best_s < best_p) return Hit{best_s, win_s};
     if (win_p >= 0) return Hit{best_p, ~win_p};
@@ -877,13 +918,13 @@ __device__ __forceinline__ Hit nearest_direct(const LaunchParams& p, f3 o, f3 d,
 // with no plane hit, or the nearest within 0.01, the colour is Zero whatever the spheres do,
 // so they are not tested.  Returns HIT_NONE (Zero) or the plane hit (One);
 // the walk classifies it exactly as it would the full nearest hit.
-template <typename T>
+template <int PATH, typename T>
 __device__ __forceinline__ Hit terminal_direct(const LaunchParams& p, f3 o, f3 d, T& tl) {
     float best_p = __builtin_inff();
     int win_p = -1;
     for (int i = 0; i < p.P; ++i) {
         tl.plane(true);
-        plane_take(o, d, p.pl[i], i, best_p, win_p);
+        plane_take(o, d, SceneOf<PATH>::pl(p)[i], i, best_p, win_p);
     }
     if (win_p < 0 || !(best_p - 0.01f > 0.0f)) return Hit{0.0f, HIT_NONE};
     const float a = dot(d, d);
@@ -892,9 +933,9 @@ __device__ __forceinline__ Hit terminal_direct(const LaunchParams& p, f3 o, f3 d
     float best_s = __builtin_inff();
     int win_s = -1;
     if (__builtin_amdgcn_ballot_w64(!a2_ok) == 0)
-        nearest_spheres<false, true>(p, o, d, a2, a4, a2_ok, 0, best_s, win_s, tl);
+        nearest_spheres<false, true, false, PATH>(p, o, d, a2, a4, a2_ok, 0, best_s, win_s, tl);
     else
-        nearest_spheres<false, false>(p, o, d, a2, a4, a2_ok, 0, best_s, win_s, tl);
+        nearest_spheres<false, false, false, PATH>(p, o, d, a2, a4, a2_ok, 0, best_s, win_s, tl);
     if (best_s < best_p) return Hit{0.0f, HIT_NONE};  // a sphere is selected: Zero
     return Hit{best_p, ~win_p};
 }
@@ -987,9 +1028,9 @@ __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int 
                 const f3 hp = add(o, scale(d, h.t));
                 stk.push(make_float4(hp.x, hp.y, hp.z, h.t), make_float4(d.x, d.y, d.z, __int_as_float(h.prim)));
                 const int prim = is_sphere ? h.prim : ~h.prim;
-                const uint32_t flags = p.mat[is_sphere ? prim : p.S + prim].flags;
+                const uint32_t flags = SceneOf<PATH>::mat(p)[is_sphere ? prim : p.S + prim].flags;
                 if (!(flags & MAT_MIRROR)) break;
-                o = reflect_at(p, o, d, h.t, h.prim);  // :854, CalculateReflectionRay :718-720
+                o = reflect_at<PATH>(p, o, d, h.t, h.prim);  // :854, CalculateReflectionRay :718-720
                 ++count;
                 ++cnt;
                 // count is the same for every lane still walking: no divergence here
@@ -998,9 +1039,9 @@ __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int 
                     // (count read from the first active lane: a scalar branch, and the mask stays wave-uniform)
                     unsigned smask = ~0u;
                     if (vw.mbox_n() > 0 && __builtin_amdgcn_readfirstlane(count) == 1) smask = mirror_box_select<PATH>(p, mmask, h.t, h.prim, rec);
-                    h = count > p.limit ? terminal_direct(p, o, d, tl) : nearest_direct<false, true>(p, o, d, tl, smask);
+                    h = count > p.limit ? terminal_direct<PATH>(p, o, d, tl) : nearest_direct<false, true, PATH>(p, o, d, tl, smask);
                 } else {
-                    h = count > p.limit ? terminal_direct(p, o, d, tl) : nearest_direct<false>(p, o, d, tl);
+                    h = count > p.limit ? terminal_direct<PATH>(p, o, d, tl) : nearest_direct<false, false, PATH>(p, o, d, tl);
                 }
             }
             // backward fold: every recorded hit is shaded in reverse order; a mirror hit
@@ -1031,7 +1072,7 @@ __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int 
                 stk.template pop<PATH>(p, ra, rb, rec);
                 const int code = __float_as_int(rb.w);
                 const bool is_s = code >= 0;
-                col = shade_direct<GPOW>(p, is_s, is_s ? code : ~code, mk(ra.x, ra.y, ra.z),
+                col = shade_direct<GPOW, false, PATH>(p, is_s, is_s ? code : ~code, mk(ra.x, ra.y, ra.z),
                                                mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl);
             }
             if constexpr (UNIFORM) {
@@ -1039,7 +1080,7 @@ __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int 
                     float4 ra, rb;
                     stk.template level0<PATH>(p, ra, rb, rec);
                     const int plane = ~__builtin_amdgcn_readfirstlane(__float_as_int(rb.w));
-                    col = shade_plane_uniform(p, plane, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl);
+                    col = shade_plane_uniform<PATH>(p, plane, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl);
                 }
             }
             px32 = (shift_channel(col.x) << 16) | (shift_channel(col.y) << 8) | shift_channel(col.z);
@@ -1250,8 +1291,9 @@ __device__ __forceinline__ void progressive_tile(const LaunchParams& p, int tile
 // view from LaunchParams::views (one DevView per grid z).  SHUTTER: a PATH launch whose waves trace 1 <<
 // shutter_log2 views per grid z and store their mean (shutter_tile).  ADAPT: supersampling whose waves decide per
 // 8x8 output tile whether to trace more than one sample per pixel (adaptive_tile).  PROG: a progressive Tick, whose
-// waves add 0-2 samples per output pixel to the run's accumulator (progressive_tile).  All five of the plain batch
-// variants only (no STATS, no TILES, WPG 1, TORD 0: rt_internal.h trace_variant_built).
+// waves add 0-2 samples per output pixel to the run's accumulator (progressive_tile).  ANIM: a PATH launch whose
+// frame z also reads its own scene image, LaunchParams::scene_stride bytes behind frame z - 1's (SceneOf).  All six of
+// the plain batch variants only (no STATS, no TILES, WPG 1, TORD 0: rt_internal.h trace_variant_built).
 // The options arrive as one variant word V (rt_internal.h VF_*, vf_cls = SMAX) and are read from it by name.
 template <int K, unsigned V>
 __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
@@ -1435,13 +1477,14 @@ __device__ __forceinline__ Bundle make_bundle(f3 o, f3 d, bool active, bool dir_
 }
 
 // Candidate mask of spheres [base, base+n) (n <= 64) for bundle B.  Converged call.
+template <int PATH>
 __device__ __forceinline__ unsigned long long cull_mask(const LaunchParams& p, const Bundle& B, int base, int n) {
     // branch-free (no exec-mask bookkeeping on the scalar unit): every lane loads and tests, lanes
     // >= n are dropped from the ballot; a sphere is culled only when the bundle allows culling,
     // its record is in range and one of the rules holds (NaN anywhere -> candidate)
     const int lane = threadIdx.x & 63;
     const bool in = lane < n;
-    const DevSphereCull s = p.scull[base + (in ? lane : 0)];
+    const DevSphereCull s = SceneOf<PATH>::scull(p)[base + (in ? lane : 0)];
     const f3 w = sub(mk(s.cx, s.cy, s.cz), B.O);
     const float dc = clen3(w) * (1.0f + 0x1p-20f);
     const float mgn = 0x1p-8f * (dc + B.R);
@@ -1467,6 +1510,7 @@ __device__ __forceinline__ unsigned long long cull_mask(const LaunchParams& p, c
 // non-selectable.  The perpendicular distance is |w x A| (no cancellation), A = d / |d| by the hardware rsq
 // (~1 ulp, far inside the margin); the products are fused (culling-only arithmetic: fewer roundings).  A lane whose a = d.d is outside [0.5, 2] or whose origin is not finite
 // keeps every cluster, and a cluster with a NaN R (a member without a usable cull record) is never culled.
+template <int PATH>
 __device__ __forceinline__ unsigned long long cluster_mask(const LaunchParams& p, f3 o, f3 d) {
     const float a = dot(d, d);
     const f3 A = cnormalize(d);
@@ -1474,7 +1518,7 @@ __device__ __forceinline__ unsigned long long cluster_mask(const LaunchParams& p
     const bool ok = a >= 0.5f && a <= 2.0f && ol < 0x1p40f;
     unsigned long long m = 0;
     for (int j = 0; j < p.n_clus; ++j) {  // wave-uniform
-        const DevCluster c = p.clus[j];
+        const DevCluster c = SceneOf<PATH>::clus(p)[j];
         const f3 w = sub(mk(c.cx, c.cy, c.cz), o);
         const float dc = (__builtin_fabsf(w.x) + __builtin_fabsf(w.y) + __builtin_fabsf(w.z)) * (1.0f + 0x1p-20f);
         const float mgn = 0x1p-8f * (dc + c.R);
@@ -1539,16 +1583,17 @@ __device__ __forceinline__ ShadowSphere make_shadow_sphere(f3 hp, bool active) {
 
 // Candidate mask of spheres [base, base+n) (n <= 64) for the shadow rays of light li from the
 // ball S.  Converged call.
+template <int PATH>
 __device__ __forceinline__ unsigned long long shadow_sphere_cull(const LaunchParams& p, const ShadowSphere& S,
                                                                  const DevLight& l, int li, int base, int n) {
     const int lane = threadIdx.x & 63;
     const bool in = lane < n;
-    const bool ok = S.ok && p.shcull != nullptr && l.a >= 0x1p-40f && l.a <= 0x1p40f && l.a2 < __builtin_inff();
+    const bool ok = S.ok && SceneOf<PATH>::shcull(p) != nullptr && l.a >= 0x1p-40f && l.a <= 0x1p40f && l.a2 < __builtin_inff();
     if (!ok) return __builtin_amdgcn_ballot_w64(in);  // (uniform) no culling: every sphere is a candidate
     // O in the light's frame (uniform); branch-free per lane, as cull_mask
     const float ou = dot(S.O, mk(l.ux, l.uy, l.uz)), ov = dot(S.O, mk(l.vx, l.vy, l.vz));
     const float oa = dot(S.O, mk(l.ax, l.ay, l.az));
-    const DevShadowCull c = p.shcull[(size_t)li * (size_t)p.S + (size_t)(base + (in ? lane : 0))];
+    const DevShadowCull c = SceneOf<PATH>::shcull(p)[(size_t)li * (size_t)p.S + (size_t)(base + (in ? lane : 0))];
     const float wu = c.cu - ou, wv = c.cv - ov, wa = c.ca - oa;
     const float dc = __builtin_fabsf(wu) + __builtin_fabsf(wv) + __builtin_fabsf(wa);  // >= |C - O|
     const float mgn = 0x1p-8f * (dc + 3.0f * S.R) + S.omgn;
@@ -1562,7 +1607,7 @@ __device__ __forceinline__ unsigned long long shadow_sphere_cull(const LaunchPar
 // Exact tests of the candidate spheres m (bits relative to `base`) of one bundle segment, in
 // ascending order (the reference's tie rules), for every lane (idle lanes trace a copy of an active
 // lane's ray).  A2OK: 2a finite-positive on every lane.
-template <bool PRIMARY, bool A2OK, int PATH = VIEW_ARGS, typename T>
+template <bool PRIMARY, bool A2OK, int PATH, typename T>
 __device__ __forceinline__ void bundle_candidates(const LaunchParams& p, unsigned long long m, int base, f3 o, f3 d,
                                                   float a2, float a4, bool a2_ok, bool active, float& best_s,
                                                   int& win_s, T& tl, int rec = 0) {
@@ -1574,7 +1619,7 @@ __device__ __forceinline__ void bundle_candidates(const LaunchParams& p, unsigne
             const float disc = b * b - a4 * pc.c;
             return A2OK ? root_t1(b, disc, a2) : (a2_ok ? root_t1(b, disc, a2) : root_full(b, disc, a2));
         }
-        return sphere_t<A2OK>(o, d, a2, a4, a2_ok, p.sph[i]);
+        return sphere_t<A2OK>(o, d, a2, a4, a2_ok, SceneOf<PATH>::sph(p)[i]);
     };
     auto take = [&](float t, int i) {
         if (PRIMARY) take_primary(t, i, best_s, win_s);
@@ -1605,7 +1650,7 @@ __device__ __forceinline__ void bundle_candidates(const LaunchParams& p, unsigne
 // rule (:977, :987, :993) with the per-frame camera-relative constants; otherwise
 // TraceSecondaryRay's asymmetric rule (:804-806, :819-821, :825).
 // `planes`: the segment's nearest plane hit when the caller already has it (terminal segments).
-template <bool PRIMARY, int PATH = VIEW_ARGS, typename T>
+template <bool PRIMARY, int PATH, typename T>
 __device__ __forceinline__ Hit nearest_bundle(const LaunchParams& p, f3 o, f3 d, bool active, T& tl,
                                               unsigned long long pmask = 0, const Hit* planes = nullptr, int rec = 0) {
     const unsigned long long am = __builtin_amdgcn_ballot_w64(active);
@@ -1635,7 +1680,7 @@ __device__ __forceinline__ Hit nearest_bundle(const LaunchParams& p, f3 o, f3 d,
         // less eagerly measured +2 %).  Wave-uniform.
         // A cone too wide for the bundle cull: the per-lane cluster pre-cull when the scene has clusters (S <= 64).
         const unsigned long long all = n == 64 ? ~0ull : (1ull << n) - 1ull;
-        unsigned long long m = use_box ? pmask : B.ok ? cull_mask(p, B, base, n) : p.n_clus ? cluster_mask(p, o, d) & all : all;
+        unsigned long long m = use_box ? pmask : B.ok ? cull_mask<PATH>(p, B, base, n) : p.n_clus ? cluster_mask<PATH>(p, o, d) & all : all;
         // candidates in ascending order, selection by selects (take_*, no per-lane branches); the
         // root sequence is chosen once per wave (2a finite-positive on every lane: the usual case)
         if (__builtin_amdgcn_ballot_w64(!a2_ok) == 0)
@@ -1651,7 +1696,7 @@ __device__ __forceinline__ Hit nearest_bundle(const LaunchParams& p, f3 o, f3 d,
     } else {
         for (int i = 0; i < p.P; ++i) {
             tl.plane(active);
-            plane_take(o, d, p.pl[i], i, best_p, win_p);  // t > 0 && t < best
+            plane_take(o, d, SceneOf<PATH>::pl(p)[i], i, best_p, win_p);  // t > 0 && t < best
         }
     }
     if (!active) return Hit{0.0f, HIT_NONE};
@@ -1682,10 +1727,11 @@ __device__ __forceinline__ Hit nearest_bundle(const LaunchParams& p, f3 o, f3 d,
 // and applies the same two rules: line miss if |w_perp|^2 > T^2, behind if w.A < -(R + mgn).  The
 // margins are shadow_sphere_cull's: 2^-8 (dc + 3R) with dc from the unprojected w, plus 2^-18
 // (|O| + |C|_1) for the rounding of w and of its projections (each < 2^-21 |w|_1, far inside).
+template <int PATH>
 __device__ __forceinline__ unsigned shadow_members_fast(const LaunchParams& p, const ShadowSphere& SS, unsigned want) {
     const int lane = threadIdx.x & 63;
     const bool in = lane < p.S;
-    const DevSphereCull c = p.scull[in ? lane : 0];
+    const DevSphereCull c = SceneOf<PATH>::scull(p)[in ? lane : 0];
     const f3 w = sub(mk(c.cx, c.cy, c.cz), SS.O);
     const float dc = (__builtin_fabsf(w.x) + __builtin_fabsf(w.y) + __builtin_fabsf(w.z)) * (1.0f + 0x1p-20f);
     const float c1 = __builtin_fabsf(c.cx) + __builtin_fabsf(c.cy) + __builtin_fabsf(c.cz);
@@ -1693,12 +1739,12 @@ __device__ __forceinline__ unsigned shadow_members_fast(const LaunchParams& p, c
     const float T = SS.R + c.rr + mgn;
     const float T2 = T * T, nb = -(SS.R + mgn);
     // NaN anywhere -> candidate; a ball that allows no culling keeps every sphere
-    const bool valid = SS.ok && p.shcull != nullptr && c.rr >= 0x1p-50f && dc >= 0x1p-30f && dc < 0x1p40f &&
+    const bool valid = SS.ok && SceneOf<PATH>::shcull(p) != nullptr && c.rr >= 0x1p-50f && dc >= 0x1p-30f && dc < 0x1p40f &&
                        c1 < 0x1p40f;
     unsigned memb = 0;
     for (int li = 0; li < p.L; ++li) {
         if (__builtin_amdgcn_ballot_w64((want >> li) & 1u) == 0) continue;  // wave-uniform
-        const DevLight& l = p.li[li];
+        const DevLight& l = SceneOf<PATH>::li(p)[li];
         const bool l_ok = l.a >= 0x1p-40f && l.a <= 0x1p40f && l.a2 < __builtin_inff();  // wave-uniform
         const float wu = __builtin_fmaf(w.z, l.uz, __builtin_fmaf(w.y, l.uy, w.x * l.ux));
         const float wv = __builtin_fmaf(w.z, l.vz, __builtin_fmaf(w.y, l.vy, w.x * l.vx));
@@ -1732,6 +1778,7 @@ constexpr int GRID_FROM_LEVEL = 1;
 // points of a wave scatter over the scene; tools/shadow_cull_model.py: C4 sphere-light pairs per
 // wave 27.4 -> 7.2).  Culling-only arithmetic (FMA allowed; the margins cover the projections'
 // rounding).  Same result layout as shadow_members.  Converged call.
+template <int PATH>
 __device__ __forceinline__ unsigned shadow_members_grid(const LaunchParams& p, f3 hp, unsigned want) {
     const int lane = threadIdx.x & 63;
     const float l1 = __builtin_fabsf(hp.x) + __builtin_fabsf(hp.y) + __builtin_fabsf(hp.z);
@@ -1739,8 +1786,8 @@ __device__ __forceinline__ unsigned shadow_members_grid(const LaunchParams& p, f
     for (int li = 0; li < p.L; ++li) {
         const bool w = (want >> li) & 1u;
         if (__builtin_amdgcn_ballot_w64(w) == 0) continue;  // wave-uniform
-        const DevShadowGrid& g = p.shg[li];
-        const DevLight& l = p.li[li];
+        const DevShadowGrid& g = SceneOf<PATH>::shg(p)[li];
+        const DevLight& l = SceneOf<PATH>::li(p)[li];
         const float u = __builtin_fmaf(hp.z, l.uz, __builtin_fmaf(hp.y, l.uy, hp.x * l.ux));
         const float v = __builtin_fmaf(hp.z, l.vz, __builtin_fmaf(hp.y, l.vy, hp.x * l.vx));
         const float a = __builtin_fmaf(hp.z, l.az, __builtin_fmaf(hp.y, l.ay, hp.x * l.ax));
@@ -1751,13 +1798,13 @@ __device__ __forceinline__ unsigned shadow_members_grid(const LaunchParams& p, f
         const bool in_grid = (xu >= 0.0f) & (xu < (float)SHGRID_N) & (xv >= 0.0f) & (xv < (float)SHGRID_N);
         const unsigned iu = (unsigned)__builtin_fminf(__builtin_fmaxf(xu, 0.0f), (float)(SHGRID_N - 1));
         const unsigned iv = (unsigned)__builtin_fminf(__builtin_fmaxf(xv, 0.0f), (float)(SHGRID_N - 1));
-        const unsigned long long cell = p.shgrid[(unsigned)li * (SHGRID_N * SHGRID_N) + iv * SHGRID_N + iu];
+        const unsigned long long cell = SceneOf<PATH>::shgrid(p)[(unsigned)li * (SHGRID_N * SHGRID_N) + iv * SHGRID_N + iu];
         // slab of a (far lanes: lowered by their extra margin); NaN and below the range: entry 0 (all)
         const float mg = g.far_k * l1;
         const float af = near ? a : a - (mg - g.far_b);
         const float xa = __builtin_fminf(__builtin_fmaxf(__builtin_floorf(__builtin_fmaf(af, g.sa, g.oa)), -1.0f),
                                          (float)SHGRID_SLABS);
-        const unsigned long long slab = p.shslab[(unsigned)li * (SHGRID_SLABS + 2) + (unsigned)((int)xa + 1)];
+        const unsigned long long slab = SceneOf<PATH>::shslab(p)[(unsigned)li * (SHGRID_SLABS + 2) + (unsigned)((int)xa + 1)];
         // far lanes: the box of every disc grown by the lane's own margin (NaN: inside)
         const bool out_box = (u < g.bu0 - mg) | (u > g.bu1 + mg) | (v < g.bv0 - mg) | (v > g.bv1 + mg);
         const bool take = w & (near ? in_grid : !out_box);
@@ -1772,7 +1819,7 @@ __device__ __forceinline__ unsigned shadow_members_grid(const LaunchParams& p, f
 // A2OK: every light of the scene has 2a = 2 p.p finite and > 0 (LaunchParams::lights_a2_ok, host-checked; the
 // kernel instantiation MERGED == 2): no per-light uniform check and no literal-formula fallback in the loop
 // (C4 -0.4 %, C5 -0.4 %, profiles/ab/r05_merged_loop_ab.txt).
-template <bool A2OK, typename T>
+template <bool A2OK, int PATH, typename T>
 __device__ __forceinline__ unsigned shadow_merged(const LaunchParams& p, unsigned memb, f3 hp, unsigned want, bool diff,
                                                   bool act, T& tl) {
     unsigned long long U = __builtin_amdgcn_ballot_w64(memb != 0u);
@@ -1781,7 +1828,7 @@ __device__ __forceinline__ unsigned shadow_merged(const LaunchParams& p, unsigne
         const int i = (int)__builtin_ctzll(U);
         U &= U - 1;
         const unsigned mi = (unsigned)__builtin_amdgcn_readlane((int)memb, i);  // lights with sphere i
-        const DevSphere sp = p.sph[i];
+        const DevSphere sp = SceneOf<PATH>::sph(p)[i];
         const f3 oc = sub(hp, mk(sp.cx, sp.cy, sp.cz));  // shared by the lights (shadow_blocked's oc, c)
         const float c = dot(oc, oc) - sp.r2;
 #pragma unroll
@@ -1791,7 +1838,7 @@ __device__ __forceinline__ unsigned shadow_merged(const LaunchParams& p, unsigne
             if (__builtin_amdgcn_ballot_w64(pending) == 0) continue;  // wave-uniform
             tl.shadow_cat(pending ? 0 : (((want >> li) & 1u) ? 1 : (diff ? 2 : (act ? 3 : 4))), 1u);
             tl.shadow_sphere(pending);
-            const DevLight& l = p.li[li];
+            const DevLight& l = SceneOf<PATH>::li(p)[li];
             const float b = 2.0f * dot(oc, mk(l.px, l.py, l.pz));
             const float disc = b * b - l.a4 * c;
             bool hit = false;
@@ -1818,11 +1865,11 @@ __device__ __forceinline__ unsigned shadow_merged(const LaunchParams& p, unsigne
 // the deeper segment `sec`), then each light in order, then ambient.  Inactive lanes
 // return `sec` unchanged.  Shadow rays (IntersectShadowLight :573-582) of the lanes that
 // need them form one bundle per light (common direction = the light position).
-template <bool GPOW, int MERGED, typename T>
+template <bool GPOW, int MERGED, int PATH, typename T>
 __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool is_sphere, int prim, f3 hp, f3 d, float t,
                                            f3 sec, unsigned* n_shadow, T& tl, int level) {
     // idle lanes (act false) carry a copy of an active lane's record: same branches, result dropped
-    const DevMaterial& m = p.mat[is_sphere ? prim : p.S + prim];
+    const DevMaterial& m = SceneOf<PATH>::mat(p)[is_sphere ? prim : p.S + prim];
     const uint32_t flags = m.flags;
     const bool diff = act && (flags & MAT_DIFFUSE) != 0;
     // checkerboard, :766-770: ((int)u + (int)v) & 1, unchecked int add -- first, for the dark-tile skip: a
@@ -1831,7 +1878,7 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
     float tile = 1.0f;
     bool dark = false;
     if (!is_sphere) {
-        const DevPlane& pl = p.pl[prim];
+        const DevPlane& pl = SceneOf<PATH>::pl(p)[prim];
         const float u = dot(mk(pl.e1x, pl.e1y, pl.e1z), hp);
         const float v = dot(mk(pl.e2x, pl.e2y, pl.e2z), hp);
         tile = checker_tile(u, v);
@@ -1857,23 +1904,23 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
         // lie within one grid cell of their centre (light 0's cell size), the grid otherwise (C4 -1.3 %,
         // C5 -1.6 % against the grid there, profiles/ab/r04_adaptive_level1.txt).  Wave-uniform choices.
         unsigned memb;
-        if (p.shg && level > GRID_FROM_LEVEL) {
-            memb = shadow_members_grid(p, hp, want);
-        } else if (p.shg && level == GRID_FROM_LEVEL) {
+        if (SceneOf<PATH>::shg(p) && level > GRID_FROM_LEVEL) {
+            memb = shadow_members_grid<PATH>(p, hp, want);
+        } else if (SceneOf<PATH>::shg(p) && level == GRID_FROM_LEVEL) {
             const ShadowSphere SS = make_shadow_sphere(hp, lit);
-            const float cell = 1.0f / __builtin_fmaxf(p.shg[0].su, p.shg[0].sv);
-            memb = SS.ok && SS.R < cell ? shadow_members_fast(p, SS, want) : shadow_members_grid(p, hp, want);
+            const float cell = 1.0f / __builtin_fmaxf(SceneOf<PATH>::shg(p)[0].su, SceneOf<PATH>::shg(p)[0].sv);
+            memb = SS.ok && SS.R < cell ? shadow_members_fast<PATH>(p, SS, want) : shadow_members_grid<PATH>(p, hp, want);
         } else {
-            memb = shadow_members_fast(p, make_shadow_sphere(hp, lit), want);
+            memb = shadow_members_fast<PATH>(p, make_shadow_sphere(hp, lit), want);
         }
-        blk = shadow_merged<MERGED == 2>(p, memb, hp, want, diff, act, tl);
+        blk = shadow_merged<MERGED == 2, PATH>(p, memb, hp, want, diff, act, tl);
     }
     f3 normal;
     if (is_sphere) {
-        const DevSphere& s = p.sph[prim];
+        const DevSphere& s = SceneOf<PATH>::sph(p)[prim];
         normal = normalize(sub(hp, mk(s.cx, s.cy, s.cz)));  // SpherePhongShading :706
     } else {
-        const DevPlane& pl = p.pl[prim];
+        const DevPlane& pl = SceneOf<PATH>::pl(p)[prim];
         normal = mk(pl.nx, pl.ny, pl.nz);
     }
     f3 col = mk(0.0f, 0.0f, 0.0f);
@@ -1890,7 +1937,7 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
         if (MERGED == 0) SS = make_shadow_sphere(hp, lit);  // one bound for every light's shadow rays
         unsigned long long umask = 0;  // (diagnostic builds: the union of the lights' candidates)
         for (int li = 0; li < p.L; ++li) {
-            const DevLight& l = p.li[li];
+            const DevLight& l = SceneOf<PATH>::li(p)[li];
             const f3 lp = mk(l.px, l.py, l.pz);
             const bool l_ok = l.a2 > 0.0f && l.a2 < __builtin_inff();  // wave-uniform
             // ShapePhongShading, :665-695 (first: it decides whether the shadow test matters)
@@ -1913,7 +1960,7 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
                 const f3 hs = need ? hp : SS.O;  // idle lanes mirror a shading lane (results ignored)
                 for (int base = 0; base < p.S; base += 64) {
                     const int n = min(64, p.S - base);
-                    unsigned long long mk64 = shadow_sphere_cull(p, SS, l, li, base, n);
+                    unsigned long long mk64 = shadow_sphere_cull<PATH>(p, SS, l, li, base, n);
                     tl.shadow_masks(5, mk64);
                     umask |= mk64;
                     // candidates two at a time: independent tests (ILP across the sqrt chains),
@@ -1925,7 +1972,7 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
                         const bool two = mk64 != 0;
                         const int i1 = two ? base + (int)__builtin_ctzll(mk64) : i0;
                         if (two) mk64 &= mk64 - 1;
-                        const DevSphere s0 = p.sph[i0], s1 = p.sph[i1];
+                        const DevSphere s0 = SceneOf<PATH>::sph(p)[i0], s1 = SceneOf<PATH>::sph(p)[i1];
                         tl.shadow_cat(need ? (blocked ? 1 : 0) : (diff ? 2 : (act ? 3 : 4)), 2u);
                         tl.shadow_sphere(!blocked);
                         const bool h0 = shadow_blocked<false, true>(hs, l, l_ok, s0);
@@ -1957,7 +2004,7 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
 // Backward fold (converged call, all 64 lanes): level by level from the deepest, every recorded
 // hit is shaded; a mirror hit consumes the colour of the segment after it (levels 0..limit push
 // at most one record each, so K = limit + 1 records suffice).  Returns the lane's colour.
-template <bool GPOW, int MERGED, int PATH = VIEW_ARGS, typename STK, typename T>
+template <bool GPOW, int MERGED, int PATH, typename STK, typename T>
 __device__ __forceinline__ f3 fold_converged(const LaunchParams& p, STK& stk, f3 leaf, unsigned* cnt, T& tl, int rec = 0) {
     f3 col = leaf;
     const int depth = stk.n;
@@ -1981,7 +2028,7 @@ __device__ __forceinline__ f3 fold_converged(const LaunchParams& p, STK& stk, f3
         const int code = __float_as_int(rb.w);
         const bool is_s = code >= 0;
         tl.set_level(level);
-        col = shade_bundle<GPOW, MERGED>(p, act, is_s, is_s ? code : ~code, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z),
+        col = shade_bundle<GPOW, MERGED, PATH>(p, act, is_s, is_s ? code : ~code, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z),
                                          ra.w, col, cnt, tl, level);
     }
     return col;
@@ -2032,11 +2079,11 @@ __device__ __forceinline__ TileOut trace_tile_bundle(const LaunchParams& p, int 
                 const f3 hp = add(o, scale(d, h.t));
                 stk.push(make_float4(hp.x, hp.y, hp.z, h.t), make_float4(d.x, d.y, d.z, __int_as_float(h.prim)));
                 const int prim = is_sphere ? h.prim : ~h.prim;
-                const uint32_t flags = p.mat[is_sphere ? prim : p.S + prim].flags;
+                const uint32_t flags = SceneOf<PATH>::mat(p)[is_sphere ? prim : p.S + prim].flags;
                 if (!(flags & MAT_MIRROR)) {
                     active = false;
                 } else {
-                    o = reflect_at(p, o, d, h.t, h.prim);  // :854, CalculateReflectionRay :718-720
+                    o = reflect_at<PATH>(p, o, d, h.t, h.prim);  // :854, CalculateReflectionRay :718-720
                     ++cnt;
                 }
             }
@@ -2049,17 +2096,17 @@ __device__ __forceinline__ TileOut trace_tile_bundle(const LaunchParams& p, int 
             int win_p = -1;
             for (int i = 0; i < p.P; ++i) {
                 tl.plane(active);
-                plane_take(o, d, p.pl[i], i, best_p, win_p);  // t > 0 && t < best
+                plane_take(o, d, SceneOf<PATH>::pl(p)[i], i, best_p, win_p);  // t > 0 && t < best
             }
             const bool need = active && win_p >= 0 && best_p - 0.01f > 0.0f;
             h = Hit{0.0f, HIT_NONE};
             if (__builtin_amdgcn_ballot_w64(need) != 0) {
                 const Hit pl{best_p, win_p};  // (idle lanes: replaced by a copy of an active lane's ray)
-                const Hit hn = nearest_bundle<false>(p, o, d, need, tl, 0, &pl);
+                const Hit hn = nearest_bundle<false, PATH>(p, o, d, need, tl, 0, &pl);
                 if (need) h = hn;
             }
         } else {
-            h = nearest_bundle<false>(p, o, d, active, tl);
+            h = nearest_bundle<false, PATH>(p, o, d, active, tl);
         }
     }
 
@@ -2154,6 +2201,7 @@ __device__ __forceinline__ void append_segment(DevSegment* out, int cap, unsigne
 
 __global__ __launch_bounds__(256) void debug_segments_kernel(LaunchParams p, int stride, DevSegment* out, int cap,
                                                              unsigned* count) {
+    constexpr int PATH = VIEW_ARGS;  // (the launch's own view and scene image)
     const long long idx = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * (long long)stride;
     if (idx >= (long long)p.W * p.H) return;
     const int x = (int)(idx % p.W), y = (int)(idx / p.W);
@@ -2166,7 +2214,7 @@ __global__ __launch_bounds__(256) void debug_segments_kernel(LaunchParams p, int
     f3 d = normalize(sub(vp, cam));
     f3 o = cam;
     Tally<false> tl;
-    Hit h = nearest_direct<true>(p, o, d, tl, p.S >= 64 ? ~0ull : (1ull << p.S) - 1);  // every sphere
+    Hit h = nearest_direct<true, false, VIEW_ARGS>(p, o, d, tl, p.S >= 64 ? ~0ull : (1ull << p.S) - 1);  // every sphere
     for (int level = 0;; ++level) {
         const bool none = h.prim == HIT_NONE;
         append_segment(out, cap, count, o, add(o, scale(d, none ? 100.0f : h.t)), level == 0 ? 0 : 1,
@@ -2175,18 +2223,18 @@ __global__ __launch_bounds__(256) void debug_segments_kernel(LaunchParams p, int
         const bool is_sphere = h.prim >= 0;
         const int prim = is_sphere ? h.prim : ~h.prim;
         const f3 hp = add(o, scale(d, h.t));
-        const DevMaterial& m = p.mat[is_sphere ? prim : p.S + prim];
+        const DevMaterial& m = SceneOf<PATH>::mat(p)[is_sphere ? prim : p.S + prim];
         if (m.flags & MAT_DIFFUSE) {
             for (int li = 0; li < p.L; ++li) {  // IntersectShadowLight's ray per light
-                const DevLight& l = p.li[li];
+                const DevLight& l = SceneOf<PATH>::li(p)[li];
                 const bool l_ok = l.a2 > 0.0f && l.a2 < __builtin_inff();
                 const f3 lp = mk(l.px, l.py, l.pz);
                 float tb = 1.0f;
                 for (int i = 0; i < p.S; ++i) {
-                    if (shadow_blocked<false>(hp, l, l_ok, p.sph[i])) {
-                        const f3 oc = sub(hp, mk(p.sph[i].cx, p.sph[i].cy, p.sph[i].cz));
+                    if (shadow_blocked<false>(hp, l, l_ok, SceneOf<PATH>::sph(p)[i])) {
+                        const f3 oc = sub(hp, mk(SceneOf<PATH>::sph(p)[i].cx, SceneOf<PATH>::sph(p)[i].cy, SceneOf<PATH>::sph(p)[i].cz));
                         const float b = 2.0f * dot(oc, lp);
-                        const float c = dot(oc, oc) - p.sph[i].r2;
+                        const float c = dot(oc, oc) - SceneOf<PATH>::sph(p)[i].r2;
                         const float sq = __builtin_sqrtf(b * b - l.a4 * c);
                         tb = (-b - sq) / l.a2;
                         break;
@@ -2196,11 +2244,11 @@ __global__ __launch_bounds__(256) void debug_segments_kernel(LaunchParams p, int
             }
         }
         if (!(m.flags & MAT_MIRROR)) break;
-        const f3 normal = is_sphere ? normalize(sub(hp, mk(p.sph[prim].cx, p.sph[prim].cy, p.sph[prim].cz)))
-                                    : mk(p.pl[prim].nx, p.pl[prim].ny, p.pl[prim].nz);
+        const f3 normal = is_sphere ? normalize(sub(hp, mk(SceneOf<PATH>::sph(p)[prim].cx, SceneOf<PATH>::sph(p)[prim].cy, SceneOf<PATH>::sph(p)[prim].cz)))
+                                    : mk(SceneOf<PATH>::pl(p)[prim].nx, SceneOf<PATH>::pl(p)[prim].ny, SceneOf<PATH>::pl(p)[prim].nz);
         d = sub(d, scale(normal, 2.0f * dot(d, normal)));
         o = hp;
-        h = nearest_direct<false>(p, o, d, tl);
+        h = nearest_direct<false, false, VIEW_ARGS>(p, o, d, tl);
     }
 }
 
@@ -2299,7 +2347,7 @@ int launch_trace(const LaunchParams& p, bool generic_pow, bool stats, void* stre
     auto leaf = [&](auto consts) { return launch_built(consts, p, grid, block, (hipStream_t)stream); };
     // (pick_trace_variant returns built descriptors only: an unbuilt one is an error, not a kernel)
     if (!peel(leaf, Vals<>{}, v.family, Vals<TV_DIRECT, TV_BUNDLE>{}, v.gpow, Vals<0, 1>{}, v.mode,
-              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT, TM_PROG>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
+              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT, TM_PROG, TM_ANIM>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
               Vals<1, 2, 4, 6, 8, 64>{}, v.wpg, Vals<1, SINGLE_WPG>{}, v.tord, Vals<0, 1, 2>{}))
         return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();

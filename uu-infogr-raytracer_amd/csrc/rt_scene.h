@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <thread>
 #include <utility>
 #include <vector>
 
@@ -637,6 +638,111 @@ inline SceneLayout scene_build(const rt_sphere* spheres, int n_spheres, const rt
         if ((mat[i].flags & MAT_SPEC) && mat[i].pow_kind == POW_GENERIC) L.generic_pow = true;
     L.host_blob = std::move(blob);
     return L;
+}
+
+// A scene track (rt_set_scene_track): the scene images of the frames of an animation, back to back at `stride` =
+// the layout's bytes.  The layout -- every off_*, every has_*, bytes -- depends on the counts and the options only,
+// never on values, so frame f's tables lie at frame 0's offsets inside slice f; track_build checks that instead of
+// assuming it.  `common` is that layout with the launch scalars of the whole track: n_clus (equal in every frame, or
+// the track is refused), lights_a2_ok the AND and generic_pow the OR over the frames -- sound because the kernels
+// picked by a false lights_a2_ok test each light's 2a where they use it, and the GPOW kernels dispatch on each
+// material's pow_kind (rt_kernel.hip shade_direct, shade_bundle, shadow_merged): both are exact for every frame.
+// `frames` keeps per frame what view building reads (rt_view.h view_build: host_sph, host_pl, the flags, and the
+// materials, as host_blob cut behind the material table); common.host_blob is empty.
+struct SceneTrack {
+    int n_frames = 0;
+    size_t stride = 0;
+    SceneLayout common;
+    std::vector<SceneLayout> frames;
+    std::vector<unsigned char> image;  // n_frames * stride bytes (the caller may drop it once uploaded)
+};
+
+enum : int { TRACK_OK = 0, TRACK_LAYOUT = 1, TRACK_CLUSTERS = 2 };
+
+inline bool track_same_layout(const SceneLayout& a, const SceneLayout& b) {
+    return a.S == b.S && a.P == b.P && a.L == b.L && a.limit == b.limit && a.off_sph == b.off_sph && a.off_mat == b.off_mat &&
+           a.off_pl == b.off_pl && a.off_li == b.off_li && a.off_cull == b.off_cull && a.off_shcull == b.off_shcull &&
+           a.bytes == b.bytes && a.off_shg == b.off_shg && a.off_shgrid == b.off_shgrid && a.off_shslab == b.off_shslab &&
+           a.off_clus == b.off_clus && a.off_shpre == b.off_shpre && a.has_shpre == b.has_shpre && a.off_shgrp == b.off_shgrp &&
+           a.has_shgrp == b.has_shgrp && a.mirror_box == b.mirror_box && a.prim_foot == b.prim_foot &&
+           a.uniform_plane == b.uniform_plane && a.has_shcull == b.has_shcull && a.has_shg == b.has_shg;
+}
+
+// The bytes of one frame's image for these counts and options (no table is built).
+inline size_t track_frame_bytes(int n_spheres, int n_planes, int n_lights, const SceneOptions& opt) {
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t s_pad = (size_t)n_spheres + (size_t)(n_spheres & 1), S = (size_t)n_spheres, P = (size_t)n_planes, L = (size_t)n_lights;
+    size_t o = al(sizeof(DevSphere) * s_pad);
+    o = al(o + sizeof(DevMaterial) * (S + P));
+    o = al(o + sizeof(DevPlane) * P);
+    o = al(o + sizeof(DevLight) * L);
+    o = al(o + sizeof(DevSphereCull) * S);
+    const bool has_shcull = (long long)n_lights * (long long)n_spheres <= SHADOW_CULL_MAX_ENTRIES;
+    const bool has_shg = merged_class(n_spheres, n_lights, true) != 0 && opt.shadow_grid;
+    o = al(o + (has_shcull ? sizeof(DevShadowCull) * L * S : 0));
+    o = al(o + (has_shg ? sizeof(DevShadowGrid) * L : 0));
+    o = al(o + (has_shg ? sizeof(unsigned long long) * SHGRID_N * SHGRID_N * L : 0));
+    o = al(o + (has_shg ? sizeof(unsigned long long) * (SHGRID_SLABS + 2) * L : 0));
+    const bool want_clus = n_spheres >= CULL_MIN_SPHERES && n_spheres <= 64 && opt.cluster_size >= 1;
+    o = al(o + (want_clus ? sizeof(DevCluster) * MAX_CLUSTERS : 0));
+    const bool has_shpre = n_spheres < CULL_MIN_SPHERES && n_lights >= 1 && opt.shadow_pre;
+    o = al(o + (has_shpre ? sizeof(DevShadowCull) * L * s_pad : 0));
+    return al(o + (has_shpre && opt.shadow_groups ? sizeof(DevShadowGroups) * L : 0)) + 256;
+}
+
+// The track of n_frames frames with these counts (arguments checked by the caller): frame f from spheres[f *
+// n_spheres ..], planes[f * n_planes ..], lights[f * n_lights ..] and ambients[f], each through scene_build with the
+// same options -- what rt_set_scene builds for that frame.  n_threads > 1: the frames are built by that many
+// threads, each frame into its own slice and record (the result does not depend on n_threads).  Returns TRACK_OK,
+// TRACK_LAYOUT (a frame's layout differs from frame 0's: a builder broke the rule above) or TRACK_CLUSTERS (cluster
+// counts differ between frames).
+inline int track_build(const rt_sphere* spheres, int n_spheres, const rt_plane* planes, int n_planes, const rt_light* lights,
+                       int n_lights, const rt_vec3* ambients, int recursion_limit, int n_frames, const SceneOptions& opt,
+                       int n_threads, SceneTrack* out) {
+    SceneTrack& T = *out;
+    T = SceneTrack{};
+    T.n_frames = n_frames;
+    T.stride = track_frame_bytes(n_spheres, n_planes, n_lights, opt);
+    T.frames.resize((size_t)n_frames);
+    T.image.resize((size_t)n_frames * T.stride);
+    std::vector<char> bad((size_t)n_frames, 0);
+    auto one = [&](int f) {
+        SceneLayout L = scene_build(spheres + (size_t)f * (size_t)n_spheres, n_spheres, planes + (size_t)f * (size_t)n_planes,
+                                    n_planes, lights + (size_t)f * (size_t)n_lights, n_lights, ambients[f], recursion_limit, opt);
+        if (L.bytes != T.stride || L.host_blob.size() != L.bytes) {
+            bad[(size_t)f] = 1;
+        } else {
+            std::memcpy(T.image.data() + (size_t)f * T.stride, L.host_blob.data(), L.bytes);
+            L.host_blob.resize(L.off_mat + sizeof(DevMaterial) * (size_t)(n_spheres + n_planes));  // (view_mirror_boxes, row_order)
+            L.host_blob.shrink_to_fit();
+        }
+        T.frames[(size_t)f] = std::move(L);
+    };
+    if (n_threads > n_frames) n_threads = n_frames;
+    if (n_threads > 1) {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < n_threads; ++t)
+            pool.emplace_back([&, t] {
+                for (int f = t; f < n_frames; f += n_threads) one(f);
+            });
+        for (std::thread& th : pool) th.join();
+    } else {
+        for (int f = 0; f < n_frames; ++f) one(f);
+    }
+    const SceneLayout& L0 = T.frames[0];
+    bool a2 = true, gp = false;
+    for (int f = 0; f < n_frames; ++f) {
+        const SceneLayout& L = T.frames[(size_t)f];
+        if (bad[(size_t)f] || !track_same_layout(L0, L)) return TRACK_LAYOUT;
+        if (L.n_clus != L0.n_clus) return TRACK_CLUSTERS;
+        a2 = a2 && L.lights_a2_ok;
+        gp = gp || L.generic_pow;
+    }
+    SceneLayout& C = T.common;
+    C = L0;
+    C.host_blob.clear(), C.host_sph.clear(), C.host_pl.clear();
+    C.lights_a2_ok = a2, C.generic_pow = gp;
+    return TRACK_OK;
 }
 
 }  // namespace rtk

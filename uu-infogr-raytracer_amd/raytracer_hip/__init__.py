@@ -16,7 +16,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi, debugview, path, scenes, supersample
+from . import abi, anim, debugview, path, scenes, supersample
 from .abi import RayTracerError, check, load_library
 from .debugview import SEGMENT_DTYPE, DebugView, surface_line, surface_print
 from .dist import bands_of
@@ -234,6 +234,52 @@ class Context:
             out = np.empty((n, height, width), dtype=np.int32)
         assert out.dtype == np.int32 and out.flags.c_contiguous and out.size == n * width * height
         self._check(self.lib.rt_render_path(self.ptr, width, height, cams, n, out.ctypes.data))
+        return out.reshape(n, height, width)
+
+    # -- animated scenes: one scene and one camera per frame ---------------------------
+    def set_scene_track(self, scenes_):
+        """rt_set_scene_track: the scene images of the frames of an animation, one per scenes.Scene of the list.  The
+        scenes have equal sphere, plane and light counts and one recursion limit (ValueError otherwise, before the C
+        call).  The context's own scene and camera are not touched."""
+        track = list(scenes_)
+        S, nS, P, nP, L, nL, A, limit, n = anim.c_track(track)
+        self._check(self.lib.rt_set_scene_track(self.ptr, S, nS, P, nP, L, nL, A, limit, n))
+        self.track = track
+
+    def clear_scene_track(self):
+        """rt_clear_scene_track: frees the track; the next anim render fails with RT_ERR_NO_SCENE."""
+        self._check(self.lib.rt_clear_scene_track(self.ptr))
+        self.track = None
+
+    def _anim_cameras(self, cameras, first_frame, n_frames):
+        if cameras is None:  # each scene's own camera
+            track = getattr(self, "track", None) or []
+            last = len(track) if n_frames is None else first_frame + n_frames
+            cameras = [sc.c_camera() for sc in track[max(first_frame, 0):last]]
+        return path.as_array(cameras)
+
+    def render_anim_bands(self, width: int, height: int, cameras, band_rows: int, band_first: int, band_step: int,
+                          d_ptr: int, frame_stride_bytes: int, fmt: int = abi.RT_BANDS_INT32, stream: int = 0,
+                          first_frame: int = 0) -> int:
+        """render_path_bands over the scene track: output frame j = track frame first_frame + j seen from cameras[j]
+        (None: the scenes' own cameras, to the end of the track), in one launch (rt_render_anim_bands)."""
+        cams = self._anim_cameras(cameras, first_frame, None)
+        nb = C.c_int(0)
+        self._check(self.lib.rt_render_anim_bands(self.ptr, width, height, cams, first_frame, len(cams), band_rows,
+                                                  band_first, band_step, C.c_void_p(d_ptr), frame_stride_bytes, fmt,
+                                                  C.c_void_p(stream), C.byref(nb)))
+        return nb.value
+
+    def render_anim(self, cameras=None, width: int = 0, height: int = 0, first_frame: int = 0,
+                    out: np.ndarray | None = None) -> np.ndarray:
+        """Whole frames of the scene track into host memory, [n, height, width] (rt_render_anim; synchronous): frame j
+        = track frame first_frame + j seen from cameras[j]; cameras None: each scene's own camera, to the track's end."""
+        cams = self._anim_cameras(cameras, first_frame, None)
+        n = len(cams)
+        if out is None:
+            out = np.empty((max(n, 1), height, width), dtype=np.int32)
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.size == max(n, 1) * width * height
+        self._check(self.lib.rt_render_anim(self.ptr, width, height, cams, first_frame, n, out.ctypes.data))
         return out.reshape(n, height, width)
 
     def render_shutter_bands(self, width: int, height: int, cameras, shutter: int, band_rows: int, band_first: int,

@@ -20,6 +20,7 @@ RT_CREATE_RCCL_GATHER = 1
 RT_CREATE_SHARED_DEVICE = 2
 RT_MAX_WORKERS = 64
 RT_MAX_PATH_FRAMES = 65535  # rt_render_path_bands / rt_render_path: frames per call (grid z)
+RT_MAX_TRACK_BYTES = 1 << 30  # rt_set_scene_track: the scene images of a track
 RT_MAX_SHUTTER = 256  # rt_render_shutter_bands / rt_render_shutter: sub-frame cameras per output frame
 RT_BANDS_INT32, RT_BANDS_RGB24, RT_BANDS_FRAME = 0, 1, 2
 RT_OK = 0
@@ -148,6 +149,12 @@ EXPORTS = [
                                           C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                           C.POINTER(C.c_int)]),
     ("rt_render_shutter", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_void_p]),
+    ("rt_set_scene_track", C.c_int, [C.c_void_p, C.POINTER(rt_sphere), C.c_int, C.POINTER(rt_plane), C.c_int,
+                                     C.POINTER(rt_light), C.c_int, C.POINTER(rt_vec3), C.c_int, C.c_int]),
+    ("rt_clear_scene_track", C.c_int, [C.c_void_p]),
+    ("rt_render_anim_bands", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    ("rt_render_anim", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_void_p]),
     ("rt_scatter_gathered", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                       C.c_int, C.c_void_p, C.c_void_p]),
     ("rt_wire_layout_of", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(rt_wire_layout)]),
