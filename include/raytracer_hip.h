@@ -214,6 +214,33 @@ int rt_set_view_height(rt_ctx* ctx, int view_height);
  * Returns RT_ERR_INVALID_ARG for a NULL ctx or any other k. */
 int rt_set_supersampling(rt_ctx* ctx, int k);
 int rt_get_supersampling(const rt_ctx* ctx, int* out_k);
+/* (ABI 10 addition) Supersampling for the camera-path, shutter and scene-track renders: k = 1 (the default, off),
+ * 2, 4 or 8.  A setting of its own, as rt_set_progressive's factor is: only rt_render_path[_bands],
+ * rt_render_shutter[_bands] and rt_render_anim[_bands] read it, and every other render ignores it.
+ * rt_set_supersampling keeps its meaning and its refusal: with it above 1 those six calls return
+ * RT_ERR_UNSUPPORTED whatever this factor is.
+ *   - Units: all arguments stay in output pixels -- width, height, band_rows, band indices, frame_stride_bytes,
+ *     rt_set_view_height, buffer sizes.
+ *   - Samples: sample (i, j) of output pixel (x, y) of frame f is the reference's pixel (k x + i, k y + j) of a
+ *     k width x k height frame rendered with frame f's camera (and, for rt_render_anim*, frame f's scene).
+ *   - Output, with a shutter of m sub-frames (m = 1 for the path and track calls): per 8-bit channel after
+ *     ShiftColor, (sum over the m sub-frames and the k*k samples + m k*k / 2) >> (log2 m + 2 log2 k) -- one rounding
+ *     of the whole mean, not a mean of means.  m = 1 is rt_set_supersampling's formula, k = 1 the shutter's.
+ *   - Shutter bound: m * k*k <= RT_MAX_SHUTTER, so that a channel's sum and its rounding term fit 16 bits; otherwise
+ *     RT_ERR_INVALID_ARG, checked with the other shutter arguments before any device call.
+ *   - Frame-size bound: (long long) k width * k height (the view height, when one is set) must not exceed
+ *     2^31 - 1; otherwise RT_ERR_INVALID_ARG.
+ *   - The trace kernels reduce each block in registers: no sample and no sub-frame reaches memory, and the frame
+ *     that leaves the device keeps its size.  rt_render_path's chunk rule counts output frames.
+ *   - k = 1: exactly the launches, kernels and bytes of the library without this call.  shutter == 1 is the path
+ *     call at every k.
+ *   - Statistics: frames and pixels count output frames and pixels; with counting on, primary_rays grows by the
+ *     traced output pixels x k*k x n_frames x shutter and reflect_rays / shadow_rays by the sum over every sample of
+ *     every sub-frame; with counting off nothing grows.
+ *   - Adaptive and progressive settings stay ignored by these calls.  Single-GPU contexts only, as before.
+ * Returns RT_ERR_INVALID_ARG for a NULL ctx or out pointer, or any other k. */
+int rt_set_path_supersampling(rt_ctx* ctx, int k);
+int rt_get_path_supersampling(const rt_ctx* ctx, int* out_k);
 /* (ABI 10 addition) Adaptive supersampling: with a threshold T in 1..256 and k > 1, only the 8x8 tiles of the
  * output whose pixels differ are supersampled (Whitted's criterion per tile); T = 0 (the default) is off -- every
  * pixel gets its k*k samples, by the kernels of rt_set_supersampling, unchanged.  At k = 1 the setting is stored
@@ -338,7 +365,9 @@ int rt_render_bands_batch(rt_ctx* ctx, int width, int height, int band_rows, int
  *   - Arguments are checked as rt_render_bands_batch checks them (single-GPU contexts only, band_rows > 0,
  *     frame_stride_bytes no smaller than a frame's output when n_frames > 1, ...); a NULL `cameras` or an
  *     n_frames <= 0 or above RT_MAX_PATH_FRAMES returns RT_ERR_INVALID_ARG.
- *   - With supersampling on (rt_set_supersampling, k > 1) both calls return RT_ERR_UNSUPPORTED.
+ *   - With supersampling on (rt_set_supersampling, k > 1) both calls return RT_ERR_UNSUPPORTED.  Their own
+ *     factor is rt_set_path_supersampling: with it above 1 every frame is box-filtered from k*k samples per pixel
+ *     in the kernel, all arguments and the output stay in output pixels, and primary_rays counts samples.
  *   - Statistics: every frame has its own rays and counts for itself -- with rt_set_counting on,
  *     reflect_rays and shadow_rays grow by the sum over the frames and primary_rays by the traced pixels x
  *     n_frames; frames, pixels and launches behave as for rt_render_bands_batch.  With counting off the
@@ -373,7 +402,10 @@ int rt_render_path(rt_ctx* ctx, int width, int height, const rt_camera* cameras,
  *   - shutter is a power of two in 1..RT_MAX_SHUTTER, and n_frames * shutter <= RT_MAX_PATH_FRAMES; otherwise
  *     RT_ERR_INVALID_ARG.  shutter == 1 is rt_render_path_bands / rt_render_path itself (the same launches).
  *   - Everything else is as for the path calls: formats, frame_stride_bytes, rt_set_view_height, the context's
- *     camera left alone, natural tile order, single-GPU contexts only, RT_ERR_UNSUPPORTED while supersampling.
+ *     camera left alone, natural tile order, single-GPU contexts only, RT_ERR_UNSUPPORTED while supersampling
+ *     (rt_set_supersampling above 1).
+ *   - rt_set_path_supersampling(k) applies: the output is the one round-half-up mean over the shutter's sub-frames
+ *     and each pixel's k*k samples, and shutter * k*k must not exceed RT_MAX_SHUTTER (RT_ERR_INVALID_ARG).
  *   - Statistics: frames and pixels count output frames and pixels, launches one per launch; with counting on,
  *     primary_rays grows by the traced pixels x n_frames x shutter and reflect_rays / shadow_rays by the sum
  *     over every sub-frame (each sub-frame counts for itself); with counting off nothing grows.
@@ -406,8 +438,9 @@ int rt_render_shutter(rt_ctx* ctx, int width, int height, const rt_camera* camer
  * differ (RT_ERR_UNSUPPORTED; the builders give equal counts for equal sphere counts).  The renders: a NULL context
  * or cameras, n_frames outside 1..RT_MAX_PATH_FRAMES (RT_ERR_INVALID_ARG); no track (RT_ERR_NO_SCENE); a bad frame
  * size, first_frame < 0 or first_frame + n_frames beyond the track (RT_ERR_INVALID_ARG); a context with more than
- * one worker (RT_ERR_INVALID_ARG); supersampling above 1 (RT_ERR_UNSUPPORTED).  Adaptive and progressive settings
- * are ignored, as the path calls ignore them.
+ * one worker (RT_ERR_INVALID_ARG); supersampling above 1 (RT_ERR_UNSUPPORTED); a sample frame above 2^31 - 1 under
+ * rt_set_path_supersampling (RT_ERR_INVALID_ARG).  Adaptive and progressive settings are ignored, as the path calls
+ * ignore them; rt_set_path_supersampling applies as it does to them, each frame's samples traced in that frame's scene.
  * Frames with a light at the origin, or with a general specular exponent, may be mixed with frames without: the
  * launch takes the kernels that are exact for every light and every exponent. */
 #define RT_MAX_TRACK_BYTES ((size_t)1 << 30)

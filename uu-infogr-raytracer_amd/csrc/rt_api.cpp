@@ -284,6 +284,7 @@ struct rt_ctx {
     int view_height = 0;  // rt_set_view_height: the view's height (0: each render's own frame height)
     int ss_log2 = 0;      // rt_set_supersampling: log2 of the factor k (0: off)
     int adapt_thr = 0;    // rt_set_adaptive_sampling: the threshold T in 1..256 (0: off); in effect while ss_log2 > 0
+    int path_ss_log2 = 0; // rt_set_path_supersampling: log2 of the factor of the path, shutter and track renders (0: off)
     // rt_set_progressive (rt_progressive.h): log2 of the factor (0: off), the run so far, the c of the last issued
     // Tick frame, and -- only while a Tick call issues its launches -- that Tick's plan (PROG_PLAIN otherwise: band,
     // batch and path renders never see one)
@@ -1261,6 +1262,20 @@ int rt_get_supersampling(const rt_ctx* ctx, int* out_k) {
     return RT_OK;
 }
 
+int rt_set_path_supersampling(rt_ctx* ctx, int k) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_set_path_supersampling: NULL context");
+    if (k != 1 && k != 2 && k != 4 && k != 8)
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_set_path_supersampling: factor %d is not 1, 2, 4 or 8", k);
+    ctx->path_ss_log2 = k == 8 ? 3 : k == 4 ? 2 : k == 2 ? 1 : 0;
+    return RT_OK;
+}
+
+int rt_get_path_supersampling(const rt_ctx* ctx, int* out_k) {
+    if (!ctx || !out_k) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_get_path_supersampling: NULL argument");
+    *out_k = 1 << ctx->path_ss_log2;
+    return RT_OK;
+}
+
 int rt_set_adaptive_sampling(rt_ctx* ctx, int threshold) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_set_adaptive_sampling: NULL context");
     if (threshold < 0 || threshold > 256)
@@ -1871,11 +1886,16 @@ int view_table_fill(rt_ctx* ctx, const rt_camera* cams, int n_views, int W, int 
 // first_frame + j: record j is built against that frame's spheres and planes -- the primary constants, the screen
 // boxes and the mirrored boxes all depend on them -- the block's scene pointers are set to that first frame's image,
 // and grid z steps through the images by LaunchParams::scene_stride (the ANIM kernels).
+// With rt_set_path_supersampling (ss = log2 k > 0) the launch works on the k W x k H sample frame as trace_bands does
+// under rt_set_supersampling: the records and the shared view tables are built for that size, H and the band rows are in
+// samples, and LaunchParams::view_ss selects the PATH_SS / SHUTTER_SS / ANIM_SS kernels, whose epilogue writes one pixel
+// per k x k block.  Everything the callers do with the output stays in output pixels.
 int trace_views(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const rt_camera* cams, int n_frames, int t,
                 int band_rows, int first, int step, void* out, size_t frame_bytes, int fmt, const SceneTrack* track,
                 int first_frame) {
     const int n_views = n_frames << t;  // (the callers bound it by RT_MAX_PATH_FRAMES)
     const int VH = ctx->view_height > 0 ? ctx->view_height : H;
+    const int ss = ctx->path_ss_log2;  // (check_path / check_anim bounded the sample frame, check_shutter m k^2)
     if (H > VH) return fail(ctx, RT_ERR_INVALID_ARG, "frame height %d above the view height %d", H, ctx->view_height);
     Device::PathSlot& ps = d.path_slot[d.path_next++ % Device::PATH_SLOTS];
     if (ps.busy) {  // the slot's last launch may still read its records
@@ -1904,33 +1924,41 @@ int trace_views(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const 
     int rc = RT_OK;
     if (track) {
         for (int j = 0; j < n_views && rc == RT_OK; ++j) {
-            rc = view_fill(ctx, track->frames[(size_t)(first_frame + j)], cams[j], W, VH, lp);
+            rc = view_fill(ctx, track->frames[(size_t)(first_frame + j)], cams[j], W << ss, VH << ss, lp);
             if (rc == RT_OK) view_record(lp, ps.h_views[j]);
         }
     } else {
-        rc = view_table_fill(ctx, cams, n_views, W, VH, lp, ps.h_views);
+        rc = view_table_fill(ctx, cams, n_views, W << ss, VH << ss, lp, ps.h_views);
     }
     if (rc != RT_OK) return rc;
-    lp.H = H;  // the rows traced; pw, ph, nearc and W are the same for every camera (lxt / lyt: view_tables)
+    lp.H = H << ss;  // the rows traced; pw, ph, nearc and W are the same for every camera (lxt / lyt: view_tables)
     if (track) {
         scene_params(ctx, d, lp, track->common, (const char*)d.d_track + (size_t)first_frame * track->stride);
         lp.scene_stride = track->stride;
     } else {
         scene_params(ctx, d, lp);
     }
-    rc = view_tables(ctx, d, lp);
+    rc = view_tables(ctx, d, lp, ss);
     if (rc != RT_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ps.d_views, ps.h_views, (size_t)n_views * sizeof(DevView), hipMemcpyHostToDevice, stream));
     const int nb = bands_of(H, band_rows, first, step);
     lp.views = ps.d_views;
     lp.shutter_log2 = t;
-    lp.band_first = first, lp.band_step = step, lp.band_rows = band_rows, lp.local_rows = nb * band_rows;
+    lp.band_first = first, lp.band_step = step;
+    if (ss > 0) {  // (as trace_bands: a band of H rows or more is the frame as band 0, so k band_rows stays below k H)
+        lp.band_rows = std::min(band_rows, H) << ss;
+        lp.local_rows = nb * lp.band_rows;
+        lp.ss_log2 = ss;
+        lp.view_ss = 1;
+    } else {
+        lp.band_rows = band_rows, lp.local_rows = nb * band_rows;
+    }
     lp.out = (int32_t*)out;
     lp.out_fmt = fmt;
     lp.n_frames = n_frames;
     lp.out_frame_bytes = frame_bytes;
-    rc = launch_counted(ctx, d, stream, lp, track ? "anim" : "path", W, H, band_rows, first, step, nb, n_views, 0,
-                        track ? (track->common.generic_pow ? 1 : 0) : -1);  // (primary rays: every sub-frame's)
+    rc = launch_counted(ctx, d, stream, lp, track ? "anim" : "path", W, H, band_rows, first, step, nb, n_views, ss,
+                        track ? (track->common.generic_pow ? 1 : 0) : -1);  // (primary rays: every sample of every sub-frame)
     if (rc != RT_OK) return rc;
     HIP_TRY(ctx, hipEventRecord(ps.done, stream));
     ps.busy = true;
@@ -1947,6 +1975,17 @@ int trace_anim(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const r
                        first_frame);
 }
 
+// rt_set_path_supersampling in effect: the k W x k VH sample frame (VH: the view height when one is set) is bounded
+// like any frame.
+int check_path_samples(rt_ctx* ctx, const char* who, int W, int H) {
+    const int s = ctx->path_ss_log2;
+    const int VH = ctx->view_height > 0 ? ctx->view_height : H;
+    if (s > 0 && ((long long)W << s) * ((long long)VH << s) > (1LL << 31) - 1)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: frame size %dx%d at path supersampling factor %d exceeds 2^31 - 1 samples", who, W,
+                    VH, 1 << s);
+    return RT_OK;
+}
+
 int check_path(rt_ctx* ctx, const char* who, int W, int H, const rt_camera* cams, int n_frames) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "NULL context");
     if (!cams || n_frames <= 0 || n_frames > RT_MAX_PATH_FRAMES)
@@ -1954,8 +1993,9 @@ int check_path(rt_ctx* ctx, const char* who, int W, int H, const rt_camera* cams
     int rc = check_ctx(ctx, W, H, false);
     if (rc != RT_OK) return rc;
     if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s needs a single-GPU context", who);
-    if (ctx->ss_log2 > 0) return fail(ctx, RT_ERR_UNSUPPORTED, "%s does not supersample", who);
-    return RT_OK;
+    if (ctx->ss_log2 > 0)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "%s does not supersample under rt_set_supersampling (rt_set_path_supersampling is its factor)", who);
+    return check_path_samples(ctx, who, W, H);
 }
 
 // check_path for the scene-track renders: the track stands where the scene does, then the frame range.
@@ -1970,8 +2010,9 @@ int check_anim(rt_ctx* ctx, const char* who, int W, int H, const rt_camera* cams
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: frames %d..%lld outside the track's %d", who, first_frame,
                     (long long)first_frame + n_frames - 1, ctx->track.n_frames);
     if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s needs a single-GPU context", who);
-    if (ctx->ss_log2 > 0) return fail(ctx, RT_ERR_UNSUPPORTED, "%s does not supersample", who);
-    return RT_OK;
+    if (ctx->ss_log2 > 0)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "%s does not supersample under rt_set_supersampling (rt_set_path_supersampling is its factor)", who);
+    return check_path_samples(ctx, who, W, H);
 }
 
 // The shutter calls' own arguments, ahead of check_path's: *t = log2(shutter).  n_frames * shutter cameras make
@@ -1983,6 +2024,10 @@ int check_shutter(rt_ctx* ctx, const char* who, int n_frames, int shutter, int* 
     if (n_frames > 0 && (long long)n_frames * shutter > RT_MAX_PATH_FRAMES)
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: %d frames x shutter %d above %d cameras", who, n_frames, shutter,
                     RT_MAX_PATH_FRAMES);
+    // (rt_set_path_supersampling: a channel's sum over the m sub-frames and the k^2 samples keeps the 16-bit fields)
+    if (((long long)shutter << (2 * ctx->path_ss_log2)) > RT_MAX_SHUTTER)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: shutter %d x path supersampling factor %d squared above %d samples per pixel", who,
+                    shutter, 1 << ctx->path_ss_log2, RT_MAX_SHUTTER);
     *t = 0;
     while ((1 << *t) < shutter) ++*t;
     return RT_OK;

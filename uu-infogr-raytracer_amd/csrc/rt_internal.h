@@ -326,6 +326,13 @@ struct LaunchParams {
     // limit, n_clus, lights_a2_ok, uniform_plane) are the same for every frame (rt_scene.h track_build).  0: every frame
     // has the scene at the pointers (a zeroed block).  Last: no other field moves.
     unsigned long long scene_stride;
+    // Supersampled path, shutter and track launches (rt_set_path_supersampling, the PATH_SS / SHUTTER_SS / ANIM_SS
+    // instantiations): 1 marks a launch with `views` and ss_log2 > 0 -- W, H, band_rows and local_rows are in samples
+    // as in any supersampling launch, the DevView records are built for the k W x k H sample frame, a lane is a sample
+    // and the epilogue writes one pixel per k x k block (rt_kernel.hip resolve_tile; with a shutter the block sum of
+    // the lanes' sub-frame sums, shutter_tile).  0: `views` with ss_log2 > 0 stays a combination no kernel is built for
+    // (a zeroed block).  Last: no other field moves.
+    int view_ss;
 };
 constexpr int MIRROR_BOX_PLANES = 2;
 // Tiles per workgroup of the direct kernel's single-frame launches (8: +2.5 % on C2,
@@ -352,8 +359,10 @@ enum : int { TV_DIRECT = 0, TV_BUNDLE = 1 };
 // PATH launch whose waves average 1 << shutter_log2 DevViews per grid z.  ADAPT: supersampling decided per output
 // tile (LaunchParams::adapt_thr).  PROG: one Tick of a progressive run, 0-2 samples per output pixel added to an
 // accumulator that outlives the launch (LaunchParams::prog_acc).  ANIM: a PATH launch whose grid z also has its own
-// scene image (LaunchParams::scene_stride).
-enum : int { TM_PLAIN = 0, TM_STATS = 1, TM_TILES = 2, TM_SS = 3, TM_PATH = 4, TM_SHUTTER = 5, TM_ADAPT = 6, TM_PROG = 7, TM_ANIM = 8 };
+// scene image (LaunchParams::scene_stride).  PATH_SS, SHUTTER_SS, ANIM_SS: the twins of PATH, SHUTTER and ANIM whose
+// lanes are samples of the k W x k H frame, with SS's tile mapping and epilogue (LaunchParams::view_ss).
+enum : int { TM_PLAIN = 0, TM_STATS = 1, TM_TILES = 2, TM_SS = 3, TM_PATH = 4, TM_SHUTTER = 5, TM_ADAPT = 6, TM_PROG = 7, TM_ANIM = 8,
+             TM_PATH_SS = 9, TM_SHUTTER_SS = 10, TM_ANIM_SS = 11 };
 struct TraceVariant {
     int family;  // TV_*
     int gpow;    // some material needs the f64 Math.Pow path: the entry points without the register caps
@@ -367,6 +376,9 @@ struct TraceVariant {
 enum : unsigned { VF_GPOW = 1u, VF_STATS = 2u, VF_TILES = 4u, VF_SS = 8u, VF_PATH = 16u, VF_SHUTTER = 32u, VF_ADAPT = 64u, VF_PROG = 128u };
 // (bits 0-7 are taken and the 4-bit fields follow: ANIM sits above vf_tord's two bits)
 constexpr unsigned VF_ANIM = 1u << 18;
+// (the supersampled twins of PATH, SHUTTER and ANIM: flags of their own, so that no earlier word changes)
+constexpr unsigned VF_PATH_SS = 1u << 19, VF_SHUTTER_SS = 1u << 20, VF_ANIM_SS = 1u << 21;
+constexpr unsigned VF_VIEW_SS = VF_PATH_SS | VF_SHUTTER_SS | VF_ANIM_SS;
 constexpr unsigned vf_cls(int c) { return (unsigned)c << 8; }
 constexpr unsigned vf_wpg(int w) { return (unsigned)w << 12; }
 constexpr unsigned vf_tord(int t) { return (unsigned)t << 16; }
@@ -378,7 +390,8 @@ constexpr unsigned variant_word(const TraceVariant& v) {
     return (v.gpow ? VF_GPOW : 0u) | (v.mode == TM_STATS ? VF_STATS : 0u) | (v.mode == TM_TILES ? VF_TILES : 0u) |
            (v.mode == TM_SS ? VF_SS : 0u) | (v.mode == TM_PATH ? VF_PATH : 0u) |
            (v.mode == TM_SHUTTER ? VF_SHUTTER : 0u) | (v.mode == TM_ADAPT ? VF_ADAPT : 0u) | (v.mode == TM_PROG ? VF_PROG : 0u) |
-           (v.mode == TM_ANIM ? VF_ANIM : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
+           (v.mode == TM_ANIM ? VF_ANIM : 0u) | (v.mode == TM_PATH_SS ? VF_PATH_SS : 0u) |
+           (v.mode == TM_SHUTTER_SS ? VF_SHUTTER_SS : 0u) | (v.mode == TM_ANIM_SS ? VF_ANIM_SS : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
 }
 
 // The bundle family's shadow pass by scene: 0 = per light (also every scene of the direct family), 1 = the
@@ -393,8 +406,9 @@ inline int merged_class(int S, int L, bool lights_a2_ok) {
 // 8-row grid when the bands are multiples of 8 output rows, or when one band covers the frame.
 inline bool adaptive_band_ok(int band_rows, int H) { return band_rows % 8 == 0 || band_rows >= H; }
 
-// The instantiations that exist (624): every mode, depth and class of both families at one tile per workgroup
-// in grid order (SHUTTER and ANIM among them, under PATH's conditions, and ADAPT and PROG, under SS's: 60 of their own each); the
+// The instantiations that exist (804): every mode, depth and class of both families at one tile per workgroup
+// in grid order (SHUTTER, ANIM, PATH_SS, SHUTTER_SS and ANIM_SS among them, under PATH's conditions, and ADAPT and PROG,
+// under SS's: 60 of their own each); the
 // direct kernel's lone-frame workgroups of SINGLE_WPG tiles in each tile order (PLAIN only); the all-lights-ok
 // merged bundle kernel's tile orders (PLAIN, no GPOW).
 constexpr bool trace_variant_built(const TraceVariant& v) {
@@ -416,10 +430,15 @@ inline bool pick_trace_variant(const LaunchParams& p, bool generic_pow, bool sta
                                   p.prog_n < 0 || p.prog_n > 2 || p.prog_first + p.prog_n < 1 ||
                                   p.prog_first + p.prog_n > 1 << (2 * p.ss_log2)))
         return false;
+    // (a supersampled path, shutter or track launch: views, a factor, and sums that fit ResolveSum's 16-bit fields)
+    if (p.view_ss != 0 && (p.view_ss != 1 || p.views == nullptr || p.ss_log2 <= 0 || p.ss_log2 > 3 ||
+                           p.shutter_log2 + 2 * p.ss_log2 > 8))
+        return false;
     if (p.views != nullptr) {
-        if (p.ss_log2 > 0 || tiles || stats || ordered || p.copy_z != 0 || p.row_order_n != 0 || p.col_major != 0)
+        if ((p.ss_log2 > 0 && p.view_ss == 0) || tiles || stats || ordered || p.copy_z != 0 || p.row_order_n != 0 || p.col_major != 0)
             return false;
-        v->mode = p.shutter_log2 > 0 ? TM_SHUTTER : p.scene_stride != 0 ? TM_ANIM : TM_PATH;
+        v->mode = p.view_ss != 0 ? (p.shutter_log2 > 0 ? TM_SHUTTER_SS : p.scene_stride != 0 ? TM_ANIM_SS : TM_PATH_SS)
+                                 : p.shutter_log2 > 0 ? TM_SHUTTER : p.scene_stride != 0 ? TM_ANIM : TM_PATH;
     } else if (p.ss_log2 > 0) {
         if (p.ss_log2 > 3 || tiles || stats || ordered || p.adapt_thr < 0 || p.adapt_thr > 256) return false;
         v->mode = p.prog_acc != nullptr ? TM_PROG : p.adapt_thr > 0 ? TM_ADAPT : TM_SS;

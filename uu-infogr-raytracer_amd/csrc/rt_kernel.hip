@@ -133,9 +133,8 @@ __device__ __forceinline__ ResolveSum resolve_add_swizzle(ResolveSum v) {
     return resolve_add(v, ResolveSum{(uint32_t)__builtin_amdgcn_ds_swizzle((int)v.rb, PATTERN),
                                      (uint32_t)__builtin_amdgcn_ds_swizzle((int)v.g, PATTERN)});
 }
-__device__ __forceinline__ void resolve_tile(const LaunchParams& p, int r, int y, int x, bool valid, uint32_t px32) {
-    const int s = p.ss_log2;
-    ResolveSum v = resolve_unpack(px32);
+// The butterfly: every lane's v -> the sum over its k x k block, k = 1 << s (in every lane of the block).
+__device__ __forceinline__ ResolveSum resolve_block_sum(ResolveSum v, int s) {
     v = resolve_add_dpp<0xb1>(v);   // quad_perm:[1,0,3,2]  lane ^ 1
     v = resolve_add_dpp<0x128>(v);  // row_ror:8            lane ^ 8
     if (s >= 2) {
@@ -146,9 +145,25 @@ __device__ __forceinline__ void resolve_tile(const LaunchParams& p, int r, int y
         v = resolve_add_swizzle<0x101f>(v);   // lane ^ 4
         v = resolve_add(v, ResolveSum{(uint32_t)__shfl_xor((int)v.rb, 32, 64), (uint32_t)__shfl_xor((int)v.g, 32, 64)});
     }
+    return v;
+}
+__device__ __forceinline__ void resolve_tile(const LaunchParams& p, int r, int y, int x, bool valid, uint32_t px32) {
+    const int s = p.ss_log2;
+    const ResolveSum v = resolve_block_sum(resolve_unpack(px32), s);
     const int km = (1 << s) - 1;
     if (valid && ((x | r) & km) == 0)  // (r and y agree modulo k: bands are multiples of k rows)
         store_at(p, (size_t)((p.out_fmt == 2 ? y : r) >> s) * (size_t)(p.W >> s) + (size_t)(x >> s), resolve_round(v, s));
+}
+// SHUTTER_SS (a shutter launch whose lanes are samples): `sum` is the lane's sample summed over the 1 << t sub-frames;
+// the block's leader stores the one round-half-up mean of all (1 << t) k^2 values, resolve_round_n over t + 2 s bits
+// (the host bounds (1 << t) k^2 by RT_MAX_SHUTTER: rt_resolve.h's 16-bit fields hold the sum and its rounding term).
+// Integer adds commute, so neither the order of the sub-frames nor that of the lanes can change a bit.
+__device__ __forceinline__ void resolve_tile_sums(const LaunchParams& p, int r, int y, int x, bool valid, ResolveSum sum, int t) {
+    const int s = p.ss_log2;
+    const ResolveSum v = resolve_block_sum(sum, s);
+    const int km = (1 << s) - 1;
+    if (valid && ((x | r) & km) == 0)
+        store_at(p, (size_t)((p.out_fmt == 2 ? y : r) >> s) * (size_t)(p.W >> s) + (size_t)(x >> s), resolve_round_n(v, t + 2 * s));
 }
 
 // OUT_TILES: the tile codec's encoder (rt_codec.hip encode_group, format raytracer_hip/tilecodec.py)
@@ -208,9 +223,16 @@ __device__ __forceinline__ void encode_tile_fused(const LaunchParams& p, uint32_
 // ANIM (scene tracks, rt_render_anim_bands): PATH's view -- every ViewOf member reads the frame's record exactly as
 // VIEW_PATH does -- in a launch whose frames also have their own scene image (SceneOf below).
 constexpr int VIEW_ARGS = 0, VIEW_PATH = 1, VIEW_SHUTTER = 2, VIEW_ANIM = 3;
+// PATH_SS, SHUTTER_SS, ANIM_SS (rt_set_path_supersampling): the view kind of the twin -- the records are built for the
+// sample frame on the host -- and, independently of it, SS's tile mapping and epilogue (ss_of).
 constexpr int view_of(unsigned V) {
-    return (V & VF_SHUTTER) ? VIEW_SHUTTER : (V & VF_ANIM) ? VIEW_ANIM : (V & VF_PATH) ? VIEW_PATH : VIEW_ARGS;
+    return (V & (VF_SHUTTER | VF_SHUTTER_SS)) ? VIEW_SHUTTER
+           : (V & (VF_ANIM | VF_ANIM_SS))     ? VIEW_ANIM
+           : (V & (VF_PATH | VF_PATH_SS))     ? VIEW_PATH
+                                              : VIEW_ARGS;
 }
+constexpr bool ss_of(unsigned V) { return (V & (VF_SS | VF_VIEW_SS)) != 0; }            // a lane is a sample of a k x k block
+constexpr bool shutter_of(unsigned V) { return (V & (VF_SHUTTER | VF_SHUTTER_SS)) != 0; }  // the sub-frame loop stores
 template <int PATH>
 struct ViewOf {
     const LaunchParams& p;
@@ -977,7 +999,7 @@ struct TileOut {
 template <int K, unsigned V, bool UNIFORM_OK = true, typename T>
 __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
                                                      float* stk_dv, T& tl, int rec = 0) {
-    constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = (V & VF_SS) != 0, SHUTTER = (V & VF_SHUTTER) != 0;
+    constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = ss_of(V), SHUTTER = shutter_of(V);
     constexpr bool ADAPT = (V & VF_ADAPT) != 0;
     constexpr int PATH = view_of(V);
     // plane-uniform waves: not in the GPOW kernels, where a second inlined pow costs an occupancy step, nor where the
@@ -1088,7 +1110,7 @@ __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int 
         if constexpr (!TILES && !SS && !SHUTTER && !ADAPT) store_pixel(p, r, y, x, px32);
     }
     if constexpr (TILES) encode_tile_fused(p, px32, valid);
-    if constexpr (SS) resolve_tile(p, r, y, x, valid, px32);
+    if constexpr (SS && !SHUTTER) resolve_tile(p, r, y, x, valid, px32);
     return TileOut{cnt, px32};
 }
 
@@ -1112,7 +1134,11 @@ __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int 
 // loop counter -- the tile position, and the address of the launch parameters, which is the kernarg segment's own
 // (every trace kernel has the one argument) -- and reads and derives what it needs inside the sub-frame, as the one
 // trace of a PATH kernel does.  The asm emits no instruction.
-template <typename F>
+// SS (SHUTTER_SS, rt_set_path_supersampling): a lane is a sample of the k W x k H frame and carries its own sample's
+// sums across the loop, exactly as above; after it the k x k block sums of those sums go through resolve_tile's
+// butterfly and the block's leader stores the single rounded mean of the m k^2 values (resolve_tile_sums).  The loop
+// itself is the same code.
+template <bool SS, typename F>
 __device__ __forceinline__ void shutter_tile(const LaunchParams& p, int tile_x, int tile_y, F trace) {
     const int t = p.shutter_log2, m = 1 << t;
     const int rec0 = (int)(blockIdx.z << t);
@@ -1134,8 +1160,9 @@ __device__ __forceinline__ void shutter_tile(const LaunchParams& p, int tile_x, 
         }
     }
     const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const TilePixel q = tile_pixel(p, tile_x * TILE_W + (ln & 7), tile_y * TILE_H + (ln >> 3));
-    if (q.valid) store_pixel(p, q.r, q.y, q.x, resolve_round_n(acc, t));
+    const TilePixel q = tile_pixel<SS>(p, tile_x * TILE_W + (ln & 7), tile_y * TILE_H + (ln >> 3));
+    if constexpr (SS) resolve_tile_sums(p, q.r, q.y, q.x, q.valid, acc, t);  // (converged: every lane is back)
+    else if (q.valid) store_pixel(p, q.r, q.y, q.x, resolve_round_n(acc, t));
     if (counting && ln == 0) {
         unsigned long long* c = &p.counters[((blockIdx.y * gridDim.x + blockIdx.x) % COUNTER_SLOTS) * COUNTER_STRIDE];
         if (n_refl) atomicAdd(c + CNT_REFLECT, n_refl);
@@ -1292,12 +1319,15 @@ __device__ __forceinline__ void progressive_tile(const LaunchParams& p, int tile
 // shutter_log2 views per grid z and store their mean (shutter_tile).  ADAPT: supersampling whose waves decide per
 // 8x8 output tile whether to trace more than one sample per pixel (adaptive_tile).  PROG: a progressive Tick, whose
 // waves add 0-2 samples per output pixel to the run's accumulator (progressive_tile).  ANIM: a PATH launch whose
-// frame z also reads its own scene image, LaunchParams::scene_stride bytes behind frame z - 1's (SceneOf).  All six of
+// frame z also reads its own scene image, LaunchParams::scene_stride bytes behind frame z - 1's (SceneOf).  PATH_SS,
+// SHUTTER_SS, ANIM_SS: PATH, SHUTTER and ANIM launches on the k W x k H sample frame (LaunchParams::view_ss) -- the
+// twin's view and scene reads with SS's tile mapping and epilogue, which the tile traces take from the word
+// independently (view_of, ss_of); SHUTTER_SS resolves the blocks of the lanes' sub-frame sums.  All nine of
 // the plain batch variants only (no STATS, no TILES, WPG 1, TORD 0: rt_internal.h trace_variant_built).
 // The options arrive as one variant word V (rt_internal.h VF_*, vf_cls = SMAX) and are read from it by name.
 template <int K, unsigned V>
 __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
-    constexpr bool STATS = (V & VF_STATS) != 0, SHUTTER = (V & VF_SHUTTER) != 0;
+    constexpr bool STATS = (V & VF_STATS) != 0, SHUTTER = shutter_of(V);
     constexpr int PATH = view_of(V);
     constexpr int SMAX = vf_cls_of(V), WPG = vf_wpg_of(V), TORD = vf_tord_of(V);
     constexpr int LDS_LEVELS = StackFor<K>::lds_levels;  // LdsStack slots, else unused
@@ -1337,7 +1367,7 @@ __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
                               in ? (unsigned)__builtin_amdgcn_s_memrealtime() : 0u};
     }
     if constexpr (SHUTTER) {
-        shutter_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int rec, int tx, int ty) { return trace_tile_direct<K, V & VF_TILE>(q, tx, ty, lv, dv, tl, rec); });
+        shutter_tile<ss_of(V)>(p, tile_x, tile_y, [&](const LaunchParams& q, int rec, int tx, int ty) { return trace_tile_direct<K, V & VF_TILE>(q, tx, ty, lv, dv, tl, rec); });
         return;
     }
     if constexpr ((V & VF_ADAPT) != 0) {
@@ -2039,7 +2069,7 @@ __device__ __forceinline__ f3 fold_converged(const LaunchParams& p, STK& stk, f3
 template <int K, unsigned V, typename T>
 __device__ __forceinline__ TileOut trace_tile_bundle(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
                                                      float* stk_dv, T& tl, int rec = 0) {
-    constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = (V & VF_SS) != 0, SHUTTER = (V & VF_SHUTTER) != 0;
+    constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = ss_of(V), SHUTTER = shutter_of(V);
     constexpr bool ADAPT = (V & VF_ADAPT) != 0;
     constexpr int PATH = view_of(V);
     constexpr int MERGED = vf_cls_of(V);
@@ -2135,7 +2165,7 @@ __device__ __forceinline__ TileOut trace_tile_bundle(const LaunchParams& p, int 
 // 2-D grid, 2 = natural and every wave records its duration in tile_cost).  V: the variant word (vf_cls = MERGED).
 template <int K, unsigned V>
 __device__ __forceinline__ void bundle_kernel_body(const LaunchParams& p) {
-    constexpr bool STATS = (V & VF_STATS) != 0, SHUTTER = (V & VF_SHUTTER) != 0;
+    constexpr bool STATS = (V & VF_STATS) != 0, SHUTTER = shutter_of(V);
     constexpr int PATH = view_of(V);
     constexpr int TORD = vf_tord_of(V);
     constexpr int LDS_LEVELS = StackFor<K>::lds_levels;  // LdsStack slots, else unused
@@ -2161,7 +2191,7 @@ __device__ __forceinline__ void bundle_kernel_body(const LaunchParams& p) {
         t_rec[0] = TileRec{blockIdx.z == (unsigned)p.copy_z ? p.tile_cost + (blockIdx.y * gridDim.x + blockIdx.x) : nullptr,
                            (unsigned)__builtin_amdgcn_s_memrealtime()};
     if constexpr (SHUTTER) {
-        shutter_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int rec, int tx, int ty) { return trace_tile_bundle<K, V & VF_TILE>(q, tx, ty, stk_lv, stk_dv, tl, rec); });
+        shutter_tile<ss_of(V)>(p, tile_x, tile_y, [&](const LaunchParams& q, int rec, int tx, int ty) { return trace_tile_bundle<K, V & VF_TILE>(q, tx, ty, stk_lv, stk_dv, tl, rec); });
         return;
     }
     if constexpr ((V & VF_ADAPT) != 0) {
@@ -2347,7 +2377,7 @@ int launch_trace(const LaunchParams& p, bool generic_pow, bool stats, void* stre
     auto leaf = [&](auto consts) { return launch_built(consts, p, grid, block, (hipStream_t)stream); };
     // (pick_trace_variant returns built descriptors only: an unbuilt one is an error, not a kernel)
     if (!peel(leaf, Vals<>{}, v.family, Vals<TV_DIRECT, TV_BUNDLE>{}, v.gpow, Vals<0, 1>{}, v.mode,
-              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT, TM_PROG, TM_ANIM>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
+              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT, TM_PROG, TM_ANIM, TM_PATH_SS, TM_SHUTTER_SS, TM_ANIM_SS>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
               Vals<1, 2, 4, 6, 8, 64>{}, v.wpg, Vals<1, SINGLE_WPG>{}, v.tord, Vals<0, 1, 2>{}))
         return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();

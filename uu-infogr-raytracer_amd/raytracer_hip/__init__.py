@@ -140,6 +140,18 @@ class Context:
         self._check(self.lib.rt_get_supersampling(self.ptr, C.byref(k)))
         return k.value
 
+    def set_path_supersampling(self, k: int):
+        """rt_set_path_supersampling: k = 1 (off), 2, 4 or 8 samples per pixel and axis for render_path[_bands],
+        render_shutter[_bands] and render_anim[_bands], resolved in the trace kernels with one rounding over the
+        shutter's sub-frames and the k x k samples (supersample.path_resolve is the definition; shutter * k * k <=
+        256).  Sizes and band arguments stay in output pixels; every other render ignores the setting."""
+        self._check(self.lib.rt_set_path_supersampling(self.ptr, int(k)))
+
+    def get_path_supersampling(self) -> int:
+        k = C.c_int(0)
+        self._check(self.lib.rt_get_path_supersampling(self.ptr, C.byref(k)))
+        return k.value
+
     def set_adaptive_sampling(self, threshold: int):
         """rt_set_adaptive_sampling: with supersampling on, only the 8x8 output tiles that hold two 4-adjacent pixels
         differing by >= threshold (1..256) in a channel are supersampled, the others keep their one sample; 0 (the

@@ -121,6 +121,8 @@ EXPORTS = [
     ("rt_set_counting", C.c_int, [C.c_void_p, C.c_int]),
     ("rt_set_supersampling", C.c_int, [C.c_void_p, C.c_int]),
     ("rt_get_supersampling", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("rt_set_path_supersampling", C.c_int, [C.c_void_p, C.c_int]),
+    ("rt_get_path_supersampling", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("rt_set_adaptive_sampling", C.c_int, [C.c_void_p, C.c_int]),
     ("rt_get_adaptive_sampling", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("rt_set_progressive", C.c_int, [C.c_void_p, C.c_int]),

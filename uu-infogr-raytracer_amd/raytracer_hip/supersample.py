@@ -28,6 +28,30 @@ def box_resolve(frame: np.ndarray, k: int) -> np.ndarray:
     return out.astype(np.int32)
 
 
+def path_resolve(sample_frames: np.ndarray, k: int, m: int = 1) -> np.ndarray:
+    """The definition of rt_set_path_supersampling: sample frames [F * m, k H, k W] of 0x00RRGGBB pixels (sub-frame s
+    of output frame f at f * m + s, each rendered at k W x k H) -> int32 [F, H, W].  Per 8-bit channel the output is
+    (sum over the m sub-frames and the k x k samples + m k k / 2) >> (log2 m + 2 log2 k): one rounding of the whole
+    mean.  m = 1 is box_resolve per frame, k = 1 is path.shutter_mean.  m: a power of two with m k k <= 256."""
+    if k not in FACTORS:
+        raise ValueError(f"supersampling factor {k} is not one of {FACTORS}")
+    if m < 1 or m & (m - 1) or m * k * k > 256:
+        raise ValueError(f"shutter {m} is not a power of two with m * k * k <= 256 (k = {k})")
+    a = np.asarray(sample_frames)
+    if a.ndim != 3 or a.shape[0] % m:
+        raise ValueError(f"sample frames {a.shape} are no [F * {m}, k H, k W]")
+    if a.shape[1] % k or a.shape[2] % k:
+        raise ValueError(f"frames with sides that are multiples of {k} are required, got {a.shape}")
+    f, h, w = a.shape[0] // m, a.shape[1] // k, a.shape[2] // k
+    n = m * k * k
+    px = a.astype(np.int64).reshape(f, m, h, k, w, k)
+    out = np.zeros((f, h, w), dtype=np.int64)
+    for shift in (16, 8, 0):
+        s = ((px >> shift) & 0xFF).sum(axis=(1, 3, 5))
+        out |= ((s + n // 2) >> (n.bit_length() - 1)) << shift
+    return out.astype(np.int32)
+
+
 # Adaptive supersampling (rt_set_adaptive_sampling): the decision is taken per 8x8 tile of the output, on the frame
 # without supersampling, which is sample (0, 0) of every k x k block.
 TILE = 8
