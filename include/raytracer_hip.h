@@ -237,7 +237,8 @@ int rt_get_supersampling(const rt_ctx* ctx, int* out_k);
  *   - Statistics: frames and pixels count output frames and pixels; with counting on, primary_rays grows by the
  *     traced output pixels x k*k x n_frames x shutter and reflect_rays / shadow_rays by the sum over every sample of
  *     every sub-frame; with counting off nothing grows.
- *   - Adaptive and progressive settings stay ignored by these calls.  Single-GPU contexts only, as before.
+ *   - rt_set_adaptive_sampling and the progressive setting stay ignored by these calls (their adaptive threshold is
+ *     rt_set_path_adaptive_sampling).  Single-GPU contexts only, as before.
  * Returns RT_ERR_INVALID_ARG for a NULL ctx or out pointer, or any other k. */
 int rt_set_path_supersampling(rt_ctx* ctx, int k);
 int rt_get_path_supersampling(const rt_ctx* ctx, int* out_k);
@@ -265,6 +266,34 @@ int rt_get_path_supersampling(const rt_ctx* ctx, int* out_k);
  * Returns RT_ERR_INVALID_ARG for a NULL ctx (or out_threshold) or a threshold outside 0..256. */
 int rt_set_adaptive_sampling(rt_ctx* ctx, int threshold);
 int rt_get_adaptive_sampling(const rt_ctx* ctx, int* out_threshold);
+/* (ABI 10 addition) Adaptive supersampling for the camera-path and scene-track renders: a threshold T of their own,
+ * 0 (the default, off) .. 256, beside rt_set_path_supersampling's factor k as rt_set_adaptive_sampling is beside
+ * rt_set_supersampling's.  Only rt_render_path[_bands], rt_render_anim[_bands] and the shutter calls read it; every
+ * other render ignores it, and rt_set_adaptive_sampling stays ignored by these six calls.
+ *   - Definition: per output frame f, rt_set_adaptive_sampling's, with P the frame the call writes at path factor 1
+ *     for frame f's camera (and, for a track, frame f's scene) and S the frame it writes at path factor k with the
+ *     threshold 0.  Tiles are the 8x8 output tiles of the rendered rows; a tile is refined iff it holds two 4-adjacent
+ *     pixels, both inside the tile and the frame, that differ by >= T in a channel of P; output = S on refined tiles,
+ *     P elsewhere.  Every frame decides for itself, in its own view and scene.
+ *   - T = 256 is the plain path frame, bit for bit.  T = 0, or k = 1, is exactly the launches, kernels and bytes of
+ *     the library without this call.
+ *   - A wave traces sample (0, 0) of its tile, decides with one ballot, and traces the other k*k - 1 samples only
+ *     when the tile is refined: nothing extra is traced for the decision, and no sample reaches memory.
+ *   - Bands: with T > 0 and k > 1 the band calls need band_rows % 8 == 0 or band_rows >= height, else
+ *     RT_ERR_UNSUPPORTED before any device call.  Under rt_set_view_height a last tile row is cut at the rendered
+ *     height, and so is its decision.
+ *   - Shutter: shutter == 1 is the path call, as everywhere.  With T > 0, k > 1 and shutter > 1 the two shutter calls
+ *     return RT_ERR_UNSUPPORTED, checked with the other shutter arguments, and write nothing: a decision on a mean of
+ *     sub-frames needs the sub-frame index and the sample pass side by side in the tile trace, which is not built.
+ *   - Statistics: frames and pixels count output frames and pixels; with counting on, primary_rays grows by the
+ *     traced output pixels x n_frames plus k*k - 1 per valid pixel of every refined tile of every frame, and
+ *     reflect_rays / shadow_rays by those samples' rays, every frame counting for itself; with counting off nothing
+ *     grows.
+ *   - Cost (1080p, 64-frame launches, counting off): see README "Adaptive paths".  Single-GPU contexts only, as the
+ *     calls themselves.
+ * Returns RT_ERR_INVALID_ARG for a NULL ctx or out pointer, or a threshold outside 0..256. */
+int rt_set_path_adaptive_sampling(rt_ctx* ctx, int threshold);
+int rt_get_path_adaptive_sampling(const rt_ctx* ctx, int* out_threshold);
 /* (ABI 10 addition) Progressive anti-aliasing for a display loop: k = 1 (the default, off), 2, 4 or 8.  While the
  * camera rests, each Tick call -- rt_render, rt_render_async, rt_render_device, and only these -- traces one more
  * sample per pixel and shows the mean so far; when anything of the view changes, the image is the plain frame again.
@@ -440,7 +469,8 @@ int rt_render_shutter(rt_ctx* ctx, int width, int height, const rt_camera* camer
  * size, first_frame < 0 or first_frame + n_frames beyond the track (RT_ERR_INVALID_ARG); a context with more than
  * one worker (RT_ERR_INVALID_ARG); supersampling above 1 (RT_ERR_UNSUPPORTED); a sample frame above 2^31 - 1 under
  * rt_set_path_supersampling (RT_ERR_INVALID_ARG).  Adaptive and progressive settings are ignored, as the path calls
- * ignore them; rt_set_path_supersampling applies as it does to them, each frame's samples traced in that frame's scene.
+ * ignore them; rt_set_path_supersampling and rt_set_path_adaptive_sampling apply as they do to them, each frame's
+ * samples traced, and each frame's tiles decided, in that frame's scene.
  * Frames with a light at the origin, or with a general specular exponent, may be mixed with frames without: the
  * launch takes the kernels that are exact for every light and every exponent. */
 #define RT_MAX_TRACK_BYTES ((size_t)1 << 30)

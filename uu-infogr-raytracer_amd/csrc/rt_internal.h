@@ -333,6 +333,13 @@ struct LaunchParams {
     // the lanes' sub-frame sums, shutter_tile).  0: `views` with ss_log2 > 0 stays a combination no kernel is built for
     // (a zeroed block).  Last: no other field moves.
     int view_ss;
+    // Adaptive path and track launches (rt_set_path_adaptive_sampling, the PATH_ADAPT / ANIM_ADAPT instantiations): the
+    // threshold T in 1..256 of a launch with `views`, view_ss = 1, ss_log2 > 0 and no shutter, 0 = none.  With it set the
+    // launch is ADAPT's per frame: a lane is an output pixel, the grid is in output tiles, the wave traces sample (0, 0) of
+    // its tile in frame z's view (and scene) and the other k^2 - 1 samples only when the tile is refined (rt_kernel.hip
+    // adaptive_tile).  adapt_thr stays ignored by a launch with `views`.  In the tail padding behind view_ss: no field
+    // moves and the block keeps its size.
+    int view_adapt;
 };
 constexpr int MIRROR_BOX_PLANES = 2;
 // Tiles per workgroup of the direct kernel's single-frame launches (8: +2.5 % on C2,
@@ -360,9 +367,10 @@ enum : int { TV_DIRECT = 0, TV_BUNDLE = 1 };
 // tile (LaunchParams::adapt_thr).  PROG: one Tick of a progressive run, 0-2 samples per output pixel added to an
 // accumulator that outlives the launch (LaunchParams::prog_acc).  ANIM: a PATH launch whose grid z also has its own
 // scene image (LaunchParams::scene_stride).  PATH_SS, SHUTTER_SS, ANIM_SS: the twins of PATH, SHUTTER and ANIM whose
-// lanes are samples of the k W x k H frame, with SS's tile mapping and epilogue (LaunchParams::view_ss).
+// lanes are samples of the k W x k H frame, with SS's tile mapping and epilogue (LaunchParams::view_ss).  PATH_ADAPT,
+// ANIM_ADAPT: PATH_SS and ANIM_SS launches that decide per output tile as ADAPT does (LaunchParams::view_adapt).
 enum : int { TM_PLAIN = 0, TM_STATS = 1, TM_TILES = 2, TM_SS = 3, TM_PATH = 4, TM_SHUTTER = 5, TM_ADAPT = 6, TM_PROG = 7, TM_ANIM = 8,
-             TM_PATH_SS = 9, TM_SHUTTER_SS = 10, TM_ANIM_SS = 11 };
+             TM_PATH_SS = 9, TM_SHUTTER_SS = 10, TM_ANIM_SS = 11, TM_PATH_ADAPT = 12, TM_ANIM_ADAPT = 13 };
 struct TraceVariant {
     int family;  // TV_*
     int gpow;    // some material needs the f64 Math.Pow path: the entry points without the register caps
@@ -379,6 +387,9 @@ constexpr unsigned VF_ANIM = 1u << 18;
 // (the supersampled twins of PATH, SHUTTER and ANIM: flags of their own, so that no earlier word changes)
 constexpr unsigned VF_PATH_SS = 1u << 19, VF_SHUTTER_SS = 1u << 20, VF_ANIM_SS = 1u << 21;
 constexpr unsigned VF_VIEW_SS = VF_PATH_SS | VF_SHUTTER_SS | VF_ANIM_SS;
+// (the adaptive twins of PATH_SS and ANIM_SS, likewise)
+constexpr unsigned VF_PATH_ADAPT = 1u << 22, VF_ANIM_ADAPT = 1u << 23;
+constexpr unsigned VF_VIEW_ADAPT = VF_PATH_ADAPT | VF_ANIM_ADAPT;
 constexpr unsigned vf_cls(int c) { return (unsigned)c << 8; }
 constexpr unsigned vf_wpg(int w) { return (unsigned)w << 12; }
 constexpr unsigned vf_tord(int t) { return (unsigned)t << 16; }
@@ -391,7 +402,8 @@ constexpr unsigned variant_word(const TraceVariant& v) {
            (v.mode == TM_SS ? VF_SS : 0u) | (v.mode == TM_PATH ? VF_PATH : 0u) |
            (v.mode == TM_SHUTTER ? VF_SHUTTER : 0u) | (v.mode == TM_ADAPT ? VF_ADAPT : 0u) | (v.mode == TM_PROG ? VF_PROG : 0u) |
            (v.mode == TM_ANIM ? VF_ANIM : 0u) | (v.mode == TM_PATH_SS ? VF_PATH_SS : 0u) |
-           (v.mode == TM_SHUTTER_SS ? VF_SHUTTER_SS : 0u) | (v.mode == TM_ANIM_SS ? VF_ANIM_SS : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
+           (v.mode == TM_SHUTTER_SS ? VF_SHUTTER_SS : 0u) | (v.mode == TM_ANIM_SS ? VF_ANIM_SS : 0u) |
+           (v.mode == TM_PATH_ADAPT ? VF_PATH_ADAPT : 0u) | (v.mode == TM_ANIM_ADAPT ? VF_ANIM_ADAPT : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
 }
 
 // The bundle family's shadow pass by scene: 0 = per light (also every scene of the direct family), 1 = the
@@ -406,9 +418,9 @@ inline int merged_class(int S, int L, bool lights_a2_ok) {
 // 8-row grid when the bands are multiples of 8 output rows, or when one band covers the frame.
 inline bool adaptive_band_ok(int band_rows, int H) { return band_rows % 8 == 0 || band_rows >= H; }
 
-// The instantiations that exist (804): every mode, depth and class of both families at one tile per workgroup
-// in grid order (SHUTTER, ANIM, PATH_SS, SHUTTER_SS and ANIM_SS among them, under PATH's conditions, and ADAPT and PROG,
-// under SS's: 60 of their own each); the
+// The instantiations that exist (924): every mode, depth and class of both families at one tile per workgroup
+// in grid order (SHUTTER, ANIM, PATH_SS, SHUTTER_SS, ANIM_SS, PATH_ADAPT and ANIM_ADAPT among them, under PATH's conditions,
+// and ADAPT and PROG, under SS's: 60 of their own each); the
 // direct kernel's lone-frame workgroups of SINGLE_WPG tiles in each tile order (PLAIN only); the all-lights-ok
 // merged bundle kernel's tile orders (PLAIN, no GPOW).
 constexpr bool trace_variant_built(const TraceVariant& v) {
@@ -434,10 +446,15 @@ inline bool pick_trace_variant(const LaunchParams& p, bool generic_pow, bool sta
     if (p.view_ss != 0 && (p.view_ss != 1 || p.views == nullptr || p.ss_log2 <= 0 || p.ss_log2 > 3 ||
                            p.shutter_log2 + 2 * p.ss_log2 > 8))
         return false;
+    // (an adaptive path or track launch: a supersampled one without a shutter, and a threshold)
+    if (p.view_adapt != 0 && (p.view_adapt < 1 || p.view_adapt > 256 || p.views == nullptr || p.view_ss != 1 || p.ss_log2 <= 0 ||
+                              p.ss_log2 > 3 || p.shutter_log2 != 0))
+        return false;
     if (p.views != nullptr) {
         if ((p.ss_log2 > 0 && p.view_ss == 0) || tiles || stats || ordered || p.copy_z != 0 || p.row_order_n != 0 || p.col_major != 0)
             return false;
-        v->mode = p.view_ss != 0 ? (p.shutter_log2 > 0 ? TM_SHUTTER_SS : p.scene_stride != 0 ? TM_ANIM_SS : TM_PATH_SS)
+        v->mode = p.view_adapt != 0 ? (p.scene_stride != 0 ? TM_ANIM_ADAPT : TM_PATH_ADAPT)
+                  : p.view_ss != 0 ? (p.shutter_log2 > 0 ? TM_SHUTTER_SS : p.scene_stride != 0 ? TM_ANIM_SS : TM_PATH_SS)
                                  : p.shutter_log2 > 0 ? TM_SHUTTER : p.scene_stride != 0 ? TM_ANIM : TM_PATH;
     } else if (p.ss_log2 > 0) {
         if (p.ss_log2 > 3 || tiles || stats || ordered || p.adapt_thr < 0 || p.adapt_thr > 256) return false;

@@ -40,7 +40,26 @@
 // or slower (C2 +0..16 %, C3 +3..22 %, C4 +16..37 %; profiles/ab/r02_tiles_per_wg_rejected.txt).
 constexpr int WG_THREADS = 64, TILE_W = 8, TILE_H = 8;
 
+// Parts.  The 924 trace instantiations take a quarter of an hour to compile as one translation unit, on one core.  The
+// Makefile therefore compiles this file RT_KERNEL_PARTS = 4 times, each time with another RT_KERNEL_PART, in parallel:
+// a part instantiates the trace kernels of its modes only (trace_mode_part) and defines launch_trace_part<its number>;
+// part 0 also holds the kernels that are no templates and every launcher, launch_trace among them, which hands a
+// descriptor to its part.  Every kernel is compiled from the same source with the same flags as in one unit; the parts'
+// objects are joined into obj/rt_kernel.o.  Without the macros (make resources, asm, variant; tools) the file is one
+// unit with everything in it.
+#ifndef RT_KERNEL_PARTS
+#define RT_KERNEL_PARTS 1
+#define RT_KERNEL_PART 0
+#endif
+static_assert((RT_KERNEL_PARTS == 1 || RT_KERNEL_PARTS == 4) && RT_KERNEL_PART >= 0 && RT_KERNEL_PART < RT_KERNEL_PARTS,
+              "one unit, or parts 0..3");
+
 namespace rtk {
+
+// PLAIN, STATS | TILES, SS, PATH, SHUTTER | ADAPT, PROG, ANIM, PATH_SS | SHUTTER_SS, ANIM_SS, PATH_ADAPT, ANIM_ADAPT:
+// 204 + 240 + 240 + 240 instantiations.
+constexpr int trace_mode_part(int mode) { return RT_KERNEL_PARTS == 1 ? 0 : mode < TM_TILES ? 0 : mode < TM_ADAPT ? 1 : mode < TM_SHUTTER_SS ? 2 : 3; }
+static_assert(TM_STATS == 1 && TM_SHUTTER == 5 && TM_PATH_SS == 9 && TM_ANIM_ADAPT == 13, "the modes of each part");
 
 // Frame / band output: int32 0x00RRGGBB at the packed band row r (format 0) or at the frame
 // row y (format 2), or packed 24-bit (B, G, R bytes; the top byte of the int32 is always 0)
@@ -94,7 +113,9 @@ __device__ __forceinline__ void copy_slice(const LaunchParams& p) {
     const size_t wg = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
     if (wg < nwg) copy_job(p.copy, wg, nwg);
 }
+#if RT_KERNEL_PART == 0
 __global__ __launch_bounds__(64) void band_copy_kernel(CopyJob j) { copy_job(j, blockIdx.x, gridDim.x); }
+#endif
 
 // Pixel i (row-major in the launch's output: packed bands, or the frame for out_fmt 2) of frame z.
 __device__ __forceinline__ void store_at(const LaunchParams& p, size_t i, uint32_t px32) {
@@ -227,12 +248,15 @@ constexpr int VIEW_ARGS = 0, VIEW_PATH = 1, VIEW_SHUTTER = 2, VIEW_ANIM = 3;
 // sample frame on the host -- and, independently of it, SS's tile mapping and epilogue (ss_of).
 constexpr int view_of(unsigned V) {
     return (V & (VF_SHUTTER | VF_SHUTTER_SS)) ? VIEW_SHUTTER
-           : (V & (VF_ANIM | VF_ANIM_SS))     ? VIEW_ANIM
-           : (V & (VF_PATH | VF_PATH_SS))     ? VIEW_PATH
+           : (V & (VF_ANIM | VF_ANIM_SS | VF_ANIM_ADAPT)) ? VIEW_ANIM
+           : (V & (VF_PATH | VF_PATH_SS | VF_PATH_ADAPT)) ? VIEW_PATH
                                               : VIEW_ARGS;
 }
 constexpr bool ss_of(unsigned V) { return (V & (VF_SS | VF_VIEW_SS)) != 0; }            // a lane is a sample of a k x k block
 constexpr bool shutter_of(unsigned V) { return (V & (VF_SHUTTER | VF_SHUTTER_SS)) != 0; }  // the sub-frame loop stores
+// PATH_ADAPT, ANIM_ADAPT (rt_set_path_adaptive_sampling): PATH's and ANIM's view and scene reads -- the records built for
+// the sample frame, as for PATH_SS -- with ADAPT's lane mapping (sample_pixel) and decision loop (adaptive_tile).
+constexpr bool adapt_of(unsigned V) { return (V & (VF_ADAPT | VF_VIEW_ADAPT)) != 0; }  // a lane is an output pixel, rec the pass
 template <int PATH>
 struct ViewOf {
     const LaunchParams& p;
@@ -995,12 +1019,13 @@ struct TileOut {
 
 // DIRECT path, one 8x8 tile: each lane walks its own chain with per-lane (divergent) control
 // flow.  rec: the sub-frame's view record (SHUTTER, wave-uniform; see ViewOf), or the sample pass (ADAPT, wave-uniform;
-// sample_pixel) -- the ADAPT kernels have the one view of the launch parameters and ViewOf never reads it.
+// sample_pixel) -- the ADAPT kernels have the one view of the launch parameters and ViewOf never reads it, and the
+// PATH_ADAPT / ANIM_ADAPT kernels' views read blockIdx.z alone.
 template <int K, unsigned V, bool UNIFORM_OK = true, typename T>
 __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
                                                      float* stk_dv, T& tl, int rec = 0) {
     constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = ss_of(V), SHUTTER = shutter_of(V);
-    constexpr bool ADAPT = (V & VF_ADAPT) != 0;
+    constexpr bool ADAPT = adapt_of(V);
     constexpr int PATH = view_of(V);
     // plane-uniform waves: not in the GPOW kernels, where a second inlined pow costs an occupancy step, nor where the
     // kernel body says so (UNIFORM_OK)
@@ -1187,7 +1212,11 @@ __device__ __forceinline__ void shutter_tile(const LaunchParams& p, int tile_x, 
 // also carries as little as it can (see below): with the factor, the threshold, the pass count and the counting
 // flag held in SGPRs across the traces the K <= 8 bundle kernels of class 0 spilled a VGPR to scratch.
 // Counting follows add_counters: frame 0 of a batch (behind a copy slice) counts for all its frames.
-template <typename F>
+// VIEWS (PATH_ADAPT, ANIM_ADAPT: rt_set_path_adaptive_sampling): every grid z is a frame with its own view (and scene),
+// so its decision and its counts are its own -- each z adds its totals once after the loop, as a PATH launch counts
+// (no copy slice in a views launch, no product with n_frames) -- and the threshold is LaunchParams::view_adapt.  The
+// loop is the same code; the view and scene of frame z are read inside the trace from blockIdx.z, never from `pass`.
+template <bool VIEWS, typename F>
 __device__ __forceinline__ void adaptive_tile(const LaunchParams& p, int tile_x, int tile_y, F trace) {
     // Carried across a trace: the pass counter, the sums (two VGPRs) and the wave's ray totals (three SGPRs: at
     // most 64 lanes x 64 segments x 64 passes reflected segments fit 32 bits).  Everything else -- the factor, the
@@ -1208,14 +1237,14 @@ __device__ __forceinline__ void adaptive_tile(const LaunchParams& p, int tile_x,
         const LaunchParams& q = *(const LaunchParams*)kp;
         const TileOut o = trace(q, s, tx, ty);
         acc = resolve_add(acc, resolve_unpack(o.px32));
-        if (q.counters != nullptr && blockIdx.z == (unsigned)q.copy_z) {  // wave-uniform
+        if (q.counters != nullptr && (VIEWS || blockIdx.z == (unsigned)q.copy_z)) {  // wave-uniform
             n_refl += wave_count(o.cnt & CNT_REFL_MASK);
             n_shadow += wave_count(o.cnt >> CNT_SHADOW_SHIFT);
         }
         if (s == 0) {  // the decision, on the frame without supersampling
             const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
             const bool valid = sample_pixel(q, tx, ty, ln, 0).valid;
-            const int thr = q.adapt_thr;
+            const int thr = VIEWS ? q.view_adapt : q.adapt_thr;
             const uint32_t v = o.px32 & 0xffffffu;
             const uint32_t left = row_shr<1>(v);                        // lane - 1: the same row for rx >= 1
             const uint32_t above = (uint32_t)__shfl_up((int)v, 8, 64);  // lane - 8: the row above
@@ -1232,13 +1261,13 @@ __device__ __forceinline__ void adaptive_tile(const LaunchParams& p, int tile_x,
     if (t.valid)  // (output coordinates: r and y agree modulo k, bands are multiples of k sample rows)
         store_at(p, (size_t)((p.out_fmt == 2 ? t.y : t.r) >> s2) * (size_t)(p.W >> s2) + (size_t)(t.x >> s2),
                  resolve_round(acc, refined ? s2 : 0));
-    if (p.counters != nullptr && blockIdx.z == (unsigned)p.copy_z) {  // wave-uniform
+    if (p.counters != nullptr && (VIEWS || blockIdx.z == (unsigned)p.copy_z)) {  // wave-uniform
         // the samples beyond one per pixel: k^2 - 1 per valid pixel of a refined tile
         const unsigned long long n_extra = refined ? (unsigned long long)((1 << (2 * s2)) - 1) *
                                                          (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(t.valid))
                                                    : 0ull;
         if (ln == 0) {
-            const unsigned long long nf = p.n_frames > 1 ? (unsigned long long)p.n_frames : 1ull;
+            const unsigned long long nf = !VIEWS && p.n_frames > 1 ? (unsigned long long)p.n_frames : 1ull;
             unsigned long long* c = &p.counters[((blockIdx.y * gridDim.x + blockIdx.x) % COUNTER_SLOTS) * COUNTER_STRIDE];
             if (n_refl) atomicAdd(c + CNT_REFLECT, n_refl * nf);
             if (n_shadow) atomicAdd(c + CNT_SHADOW, n_shadow * nf);
@@ -1322,7 +1351,8 @@ __device__ __forceinline__ void progressive_tile(const LaunchParams& p, int tile
 // frame z also reads its own scene image, LaunchParams::scene_stride bytes behind frame z - 1's (SceneOf).  PATH_SS,
 // SHUTTER_SS, ANIM_SS: PATH, SHUTTER and ANIM launches on the k W x k H sample frame (LaunchParams::view_ss) -- the
 // twin's view and scene reads with SS's tile mapping and epilogue, which the tile traces take from the word
-// independently (view_of, ss_of); SHUTTER_SS resolves the blocks of the lanes' sub-frame sums.  All nine of
+// independently (view_of, ss_of); SHUTTER_SS resolves the blocks of the lanes' sub-frame sums.  PATH_ADAPT,
+// ANIM_ADAPT: PATH_SS and ANIM_SS launches whose waves decide per output tile as ADAPT's do (adapt_of).  All eleven of
 // the plain batch variants only (no STATS, no TILES, WPG 1, TORD 0: rt_internal.h trace_variant_built).
 // The options arrive as one variant word V (rt_internal.h VF_*, vf_cls = SMAX) and are read from it by name.
 template <int K, unsigned V>
@@ -1370,8 +1400,8 @@ __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
         shutter_tile<ss_of(V)>(p, tile_x, tile_y, [&](const LaunchParams& q, int rec, int tx, int ty) { return trace_tile_direct<K, V & VF_TILE>(q, tx, ty, lv, dv, tl, rec); });
         return;
     }
-    if constexpr ((V & VF_ADAPT) != 0) {
-        adaptive_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int pass, int tx, int ty) { return trace_tile_direct<K, V & VF_TILE>(q, tx, ty, lv, dv, tl, pass); });
+    if constexpr (adapt_of(V)) {
+        adaptive_tile<PATH != VIEW_ARGS>(p, tile_x, tile_y, [&](const LaunchParams& q, int pass, int tx, int ty) { return trace_tile_direct<K, V & VF_TILE>(q, tx, ty, lv, dv, tl, pass); });
         return;
     }
     if constexpr ((V & VF_PROG) != 0) {  // (a sample is traced as ADAPT's passes are: the tile trace of that word)
@@ -2070,7 +2100,7 @@ template <int K, unsigned V, typename T>
 __device__ __forceinline__ TileOut trace_tile_bundle(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
                                                      float* stk_dv, T& tl, int rec = 0) {
     constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = ss_of(V), SHUTTER = shutter_of(V);
-    constexpr bool ADAPT = (V & VF_ADAPT) != 0;
+    constexpr bool ADAPT = adapt_of(V);
     constexpr int PATH = view_of(V);
     constexpr int MERGED = vf_cls_of(V);
     const int lane = threadIdx.x & 63;
@@ -2194,8 +2224,8 @@ __device__ __forceinline__ void bundle_kernel_body(const LaunchParams& p) {
         shutter_tile<ss_of(V)>(p, tile_x, tile_y, [&](const LaunchParams& q, int rec, int tx, int ty) { return trace_tile_bundle<K, V & VF_TILE>(q, tx, ty, stk_lv, stk_dv, tl, rec); });
         return;
     }
-    if constexpr ((V & VF_ADAPT) != 0) {
-        adaptive_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int pass, int tx, int ty) { return trace_tile_bundle<K, V & VF_TILE>(q, tx, ty, stk_lv, stk_dv, tl, pass); });
+    if constexpr (adapt_of(V)) {
+        adaptive_tile<PATH != VIEW_ARGS>(p, tile_x, tile_y, [&](const LaunchParams& q, int pass, int tx, int ty) { return trace_tile_bundle<K, V & VF_TILE>(q, tx, ty, stk_lv, stk_dv, tl, pass); });
         return;
     }
     if constexpr ((V & VF_PROG) != 0) {
@@ -2219,6 +2249,7 @@ __global__ __launch_bounds__(WG_THREADS) void trace_bundle_kernel_gpow(LaunchPar
     bundle_kernel_body<K, V>(p);
 }
 
+#if RT_KERNEL_PART == 0  // (the kernels that are no templates: once, in part 0)
 // ---------------------------------------------------------------------------------
 // Debug ray view: re-trace sampled pixels with the direct path's
 // selection rules and append their visible-path segments.  Not on the timed path.
@@ -2319,6 +2350,8 @@ __global__ __launch_bounds__(256) void scatter_gathered_kernel(const unsigned ch
     }
 }
 
+#endif  // RT_KERNEL_PART == 0
+
 // ---------------------------------------------------------------------------------
 // Trace launch: the variant (rt_internal.h pick_trace_variant), its grid, and one dispatch from the descriptor's
 // runtime fields to the instantiation.
@@ -2326,9 +2359,10 @@ __global__ __launch_bounds__(256) void scatter_gathered_kernel(const unsigned ch
 // The grid and block of a launch of variant v: one workgroup per 8x8 tile, frames (and the copy slice) in z.  A
 // lone frame on the direct kernel (wpg > 1) has wpg tiles of a tile row per workgroup, with the tile rows
 // in x when col_major is set, or a 1-D grid over the padded tile_order.
+#if RT_KERNEL_PART == 0
 static void trace_grid(const LaunchParams& p, const TraceVariant& v, dim3* grid, dim3* block) {
-    // (ADAPT, PROG: a wave is a tile of output pixels, and W, local_rows are in samples)
-    const int as = v.mode == TM_ADAPT || v.mode == TM_PROG ? p.ss_log2 : 0;
+    // (ADAPT, PROG, PATH_ADAPT, ANIM_ADAPT: a wave is a tile of output pixels, and W, local_rows are in samples)
+    const int as = v.mode == TM_ADAPT || v.mode == TM_PROG || v.mode == TM_PATH_ADAPT || v.mode == TM_ANIM_ADAPT ? p.ss_log2 : 0;
     const unsigned tx = (unsigned)(((p.W >> as) + TILE_W - 1) / TILE_W), ty = (unsigned)(((p.local_rows >> as) + TILE_H - 1) / TILE_H);
     const unsigned z = (unsigned)(p.n_frames > 1 ? p.n_frames : 1) + (unsigned)p.copy_z, w = (unsigned)v.wpg;
     const unsigned gxw = (tx + w - 1) / w;
@@ -2337,6 +2371,8 @@ static void trace_grid(const LaunchParams& p, const TraceVariant& v, dim3* grid,
     else if (p.tile_order != nullptr) *grid = dim3((tx * ty + w - 1) / w, 1u, z);
     else *grid = p.col_major ? dim3(ty, gxw, z) : dim3(gxw, ty, z);
 }
+
+#endif  // RT_KERNEL_PART == 0
 
 // peel(leaf, Vals<>{}, field, Vals<the values it takes...>{}, field, Vals<...>{}, ...): one runtime field per
 // level becomes a compile-time constant; leaf(Vals<constants...>{}) runs for the one combination that matches.
@@ -2352,12 +2388,13 @@ static bool peel(F& leaf, Vals<DONE...>, int field, Vals<VS...>, REST... rest) {
     return ((field == VS && peel(leaf, Vals<DONE..., VS>{}, rest...)) || ...);
 }
 
-// The instantiation of one descriptor, launched; false (and nothing instantiated) for one that is not built.
+// The instantiation of one descriptor, launched; false (and nothing instantiated) for one that is not built, or not in
+// this part.
 template <int FAMILY, int GPOW, int MODE, int CLS, int K, int WPG, int TORD>
 static bool launch_built(Vals<FAMILY, GPOW, MODE, CLS, K, WPG, TORD>, const LaunchParams& p, dim3 grid, dim3 block,
                          hipStream_t s) {
     constexpr TraceVariant v{FAMILY, GPOW, MODE, CLS, K, WPG, TORD};
-    if constexpr (trace_variant_built(v)) {
+    if constexpr (trace_variant_built(v) && trace_mode_part(MODE) == RT_KERNEL_PART) {
         constexpr unsigned V = variant_word(v);
         if constexpr (FAMILY == TV_DIRECT && GPOW) hipLaunchKernelGGL((trace_direct_kernel_gpow<K, V>), grid, block, 0, s, p);
         else if constexpr (FAMILY == TV_DIRECT) hipLaunchKernelGGL((trace_direct_kernel<K, V>), grid, block, 0, s, p);
@@ -2368,18 +2405,44 @@ static bool launch_built(Vals<FAMILY, GPOW, MODE, CLS, K, WPG, TORD>, const Laun
     return false;
 }
 
+// One dispatch from the descriptor's runtime fields to the instantiation, over the instantiations of part PART: each
+// part's unit defines its own.
+template <int PART>
+bool launch_trace_part(const TraceVariant& v, const LaunchParams& p, dim3 grid, dim3 block, hipStream_t s);
+template <>
+bool launch_trace_part<0>(const TraceVariant& v, const LaunchParams& p, dim3 grid, dim3 block, hipStream_t s);
+template <>
+bool launch_trace_part<1>(const TraceVariant& v, const LaunchParams& p, dim3 grid, dim3 block, hipStream_t s);
+template <>
+bool launch_trace_part<2>(const TraceVariant& v, const LaunchParams& p, dim3 grid, dim3 block, hipStream_t s);
+template <>
+bool launch_trace_part<3>(const TraceVariant& v, const LaunchParams& p, dim3 grid, dim3 block, hipStream_t s);
+
+template <>
+bool launch_trace_part<RT_KERNEL_PART>(const TraceVariant& v, const LaunchParams& p, dim3 grid, dim3 block, hipStream_t s) {
+    auto leaf = [&](auto consts) { return launch_built(consts, p, grid, block, s); };
+    return peel(leaf, Vals<>{}, v.family, Vals<TV_DIRECT, TV_BUNDLE>{}, v.gpow, Vals<0, 1>{}, v.mode,
+              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT, TM_PROG, TM_ANIM, TM_PATH_SS, TM_SHUTTER_SS, TM_ANIM_SS, TM_PATH_ADAPT, TM_ANIM_ADAPT>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
+              Vals<1, 2, 4, 6, 8, 64>{}, v.wpg, Vals<1, SINGLE_WPG>{}, v.tord, Vals<0, 1, 2>{});
+}
+
+#if RT_KERNEL_PART == 0
 int launch_trace(const LaunchParams& p, bool generic_pow, bool stats, void* stream) {
     if (p.local_rows <= 0 || p.W <= 0) return (int)hipSuccess;
     TraceVariant v;
     if (!pick_trace_variant(p, generic_pow, stats, &v)) return (int)hipErrorInvalidValue;
     dim3 grid, block;
     trace_grid(p, v, &grid, &block);
-    auto leaf = [&](auto consts) { return launch_built(consts, p, grid, block, (hipStream_t)stream); };
+    const int part = trace_mode_part(v.mode);
+    bool ok = false;
+    if (part == 0) ok = launch_trace_part<0>(v, p, grid, block, (hipStream_t)stream);
+#if RT_KERNEL_PARTS > 1
+    if (part == 1) ok = launch_trace_part<1>(v, p, grid, block, (hipStream_t)stream);
+    if (part == 2) ok = launch_trace_part<2>(v, p, grid, block, (hipStream_t)stream);
+    if (part == 3) ok = launch_trace_part<3>(v, p, grid, block, (hipStream_t)stream);
+#endif
     // (pick_trace_variant returns built descriptors only: an unbuilt one is an error, not a kernel)
-    if (!peel(leaf, Vals<>{}, v.family, Vals<TV_DIRECT, TV_BUNDLE>{}, v.gpow, Vals<0, 1>{}, v.mode,
-              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT, TM_PROG, TM_ANIM, TM_PATH_SS, TM_SHUTTER_SS, TM_ANIM_SS>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
-              Vals<1, 2, 4, 6, 8, 64>{}, v.wpg, Vals<1, SINGLE_WPG>{}, v.tord, Vals<0, 1, 2>{}))
-        return (int)hipErrorInvalidValue;
+    if (!ok) return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
@@ -2421,5 +2484,7 @@ int launch_scatter_bands(const int32_t* bands, int32_t* frame, int W, int H, int
                        W, H, band_rows, band_first, band_step, n_bands * band_rows);
     return (int)hipGetLastError();
 }
+
+#endif  // RT_KERNEL_PART == 0
 
 }  // namespace rtk

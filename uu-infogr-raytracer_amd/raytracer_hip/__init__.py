@@ -164,6 +164,18 @@ class Context:
         self._check(self.lib.rt_get_adaptive_sampling(self.ptr, C.byref(t)))
         return t.value
 
+    def set_path_adaptive_sampling(self, threshold: int):
+        """rt_set_path_adaptive_sampling: the adaptive threshold (0 = off, the default, .. 256) of render_path[_bands],
+        render_anim[_bands] and the shutter calls at a path supersampling factor above 1: per frame, only the 8x8
+        output tiles whose plain pixels differ by >= threshold are supersampled (supersample.path_adaptive_resolve is
+        the definition).  A shutter above 1 is refused while it is in effect; every other render ignores it."""
+        self._check(self.lib.rt_set_path_adaptive_sampling(self.ptr, int(threshold)))
+
+    def get_path_adaptive_sampling(self) -> int:
+        t = C.c_int(-1)
+        self._check(self.lib.rt_get_path_adaptive_sampling(self.ptr, C.byref(t)))
+        return t.value
+
     def set_progressive(self, k: int):
         """rt_set_progressive: k = 1 (off), 2, 4 or 8.  While the view rests, every Tick call (render, render_async,
         render_device) adds a sample per pixel in supersample.progressive_order(k) and returns the mean so far

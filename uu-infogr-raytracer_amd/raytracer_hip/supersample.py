@@ -97,6 +97,27 @@ def adaptive_resolve(plain: np.ndarray, samples: np.ndarray, k: int, threshold: 
     return np.where(px, full, p).astype(np.int32)
 
 
+def path_adaptive_resolve(plain_frames: np.ndarray, sample_frames: np.ndarray, k: int, threshold: int) -> np.ndarray:
+    """The definition of rt_set_path_adaptive_sampling: `plain_frames` [F, H, W] (the frames at path factor 1),
+    `sample_frames` [F, k H, k W] (the same cameras, and scenes, at k W x k H) -> int32 [F, H, W], adaptive_resolve
+    per frame: every frame decides on its own plain frame.  threshold 0 (off): path_resolve(sample_frames, k, 1)."""
+    p, s = np.asarray(plain_frames), np.asarray(sample_frames)
+    if p.ndim != 3 or s.ndim != 3 or p.shape[0] != s.shape[0]:
+        raise ValueError(f"plain frames {p.shape} and sample frames {s.shape} are no [F, H, W] and [F, k H, k W]")
+    if not 0 <= int(threshold) <= 256:
+        raise ValueError(f"adaptive threshold {threshold} is not in 0..256")
+    if k not in FACTORS:
+        raise ValueError(f"supersampling factor {k} is not one of {FACTORS}")
+    if s.shape[1:] != (p.shape[1] * k, p.shape[2] * k):
+        raise ValueError(f"plain frames {p.shape} do not match the sample frames {s.shape} at factor {k}")
+    if int(threshold) == 0:
+        return path_resolve(s, k, 1)
+    out = np.empty(p.shape, dtype=np.int32)
+    for f in range(p.shape[0]):
+        out[f] = adaptive_resolve(p[f], s[f], k, threshold)
+    return out
+
+
 # Progressive accumulation (rt_set_progressive): a resting camera's Ticks take the k x k samples of a pixel one by
 # one, coarse sub-grids first, and show the rounded mean of the samples so far.
 def progressive_order(k: int) -> list:
