@@ -483,6 +483,42 @@ int rt_render_anim_bands(rt_ctx* ctx, int width, int height, const rt_camera* ca
                          size_t frame_stride_bytes, int format, void* hip_stream, int* out_n_bands);
 int rt_render_anim(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame, int n_frames,
                    int32_t* pixels);
+/* (ABI 10 addition) Scene-track shutter: the shutter of rt_render_shutter[_bands] over a scene track, so that a
+ * moving object, a moving light and a moving camera blur alike.  Every output frame is the mean of `shutter`
+ * sub-frames, each with its own scene and its own camera, taken inside the trace kernel: `cameras` has n_frames *
+ * shutter entries, and sub-frame (f, s) is, bit for bit, the frame rt_render_anim_bands writes for track frame
+ * first_frame + f * shutter + s seen from cameras[f * shutter + s].  Output frame f is, per 8-bit channel and after
+ * ShiftColor, (sum + shutter / 2) >> log2(shutter) over its sub-frames.  first_frame need not be a multiple of
+ * shutter.  No sub-frame reaches memory and the output keeps a track render's size.
+ *   - shutter == 1 is rt_render_anim_bands / rt_render_anim itself: the same launches, kernels and bytes.
+ *   - rt_set_path_supersampling(k) applies as it does to rt_render_shutter*: one rounding (sum + m k*k / 2) >>
+ *     (log2 m + 2 log2 k) per channel over the m sub-frames and each pixel's k*k samples, and m * k*k must not
+ *     exceed RT_MAX_SHUTTER.
+ *   - With rt_set_path_adaptive_sampling in effect (a threshold, k > 1) and shutter > 1 the calls return
+ *     RT_ERR_UNSUPPORTED and write nothing, as the camera shutter does.
+ *   - Refusals, each before any device call and in this order.  First those of rt_render_anim*, in their order
+ *     above, with the track bound being first_frame + n_frames * shutter <= the track's frames: a NULL context or
+ *     cameras, n_frames outside 1..RT_MAX_PATH_FRAMES (RT_ERR_INVALID_ARG); no track (RT_ERR_NO_SCENE); a bad frame
+ *     size, first_frame < 0 or sub-frames beyond the track (RT_ERR_INVALID_ARG); a context with more than one
+ *     worker (RT_ERR_INVALID_ARG); rt_set_supersampling above 1 (RT_ERR_UNSUPPORTED); a sample frame above 2^31 - 1
+ *     (RT_ERR_INVALID_ARG).  Then the shutter's: shutter not a power of two in 1..RT_MAX_SHUTTER
+ *     (RT_ERR_INVALID_ARG); n_frames * shutter above RT_MAX_PATH_FRAMES (RT_ERR_INVALID_ARG); shutter * k*k above
+ *     RT_MAX_SHUTTER (RT_ERR_INVALID_ARG); the adaptive refusal (RT_ERR_UNSUPPORTED).  Then the band arguments, the
+ *     frame stride and a NULL pixels, as for rt_render_anim*.
+ *   - Everything else is as for the track calls: formats, frame_stride_bytes, rt_set_view_height, natural tile
+ *     order, single-GPU contexts only; the context's own scene, camera and progressive run stay untouched.
+ *   - Statistics follow the shutter's rules, each sub-frame counting for itself in its own scene: frames and pixels
+ *     count output frames and pixels; with counting on, primary_rays grows by the traced pixels x n_frames x shutter
+ *     x k*k and reflect_rays / shadow_rays by the sum over every sub-frame; with counting off nothing grows.
+ * rt_render_anim_shutter: whole output frames into host memory, pixels[n_frames][height][width], synchronous,
+ * through rt_render_path's chunk pipeline: chunks count output frames, and a chunk of nf output frames from output
+ * frame f0 takes its cameras from cameras[f0 * shutter] and its track frames from first_frame + f0 * shutter. */
+int rt_render_anim_shutter_bands(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame,
+                                 int n_frames, int shutter, int band_rows, int band_first, int band_step,
+                                 void* d_out, size_t frame_stride_bytes, int format, void* hip_stream,
+                                 int* out_n_bands);
+int rt_render_anim_shutter(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame,
+                           int n_frames, int shutter, int32_t* pixels);
 /* Reassemble the band sets of `world` ranks (band b rendered by rank b % world with
  * band_first = rank, band_step = world), gathered rank after rank at slot_bytes intervals
  * in d_gathered, into the row-major frame d_frame[height][width] -- one launch for all

@@ -1910,6 +1910,9 @@ int view_table_fill(rt_ctx* ctx, const rt_camera* cams, int n_views, int W, int 
 // first_frame + j: record j is built against that frame's spheres and planes -- the primary constants, the screen
 // boxes and the mirrored boxes all depend on them -- the block's scene pointers are set to that first frame's image,
 // and grid z steps through the images by LaunchParams::scene_stride (the ANIM kernels).
+// With both (rt_render_anim_shutter_bands: a track and t > 0) record j = f << t | s, sub-frame s of output frame f, is
+// built against track frame first_frame + j in the same way, and LaunchParams::scene_shutter marks the launch: its
+// waves step through the images by the sub-frame's record index, not by grid z (the ANIM_SHUTTER kernels).
 // With rt_set_path_supersampling (ss = log2 k > 0) the launch works on the k W x k H sample frame as trace_bands does
 // under rt_set_supersampling: the records and the shared view tables are built for that size, H and the band rows are in
 // samples, and LaunchParams::view_ss selects the PATH_SS / SHUTTER_SS / ANIM_SS kernels, whose epilogue writes one pixel
@@ -1962,6 +1965,7 @@ int trace_views(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const 
     if (track) {
         scene_params(ctx, d, lp, track->common, (const char*)d.d_track + (size_t)first_frame * track->stride);
         lp.scene_stride = track->stride;
+        lp.scene_shutter = t > 0 ? 1 : 0;
     } else {
         scene_params(ctx, d, lp);
     }
@@ -1996,10 +2000,10 @@ int trace_path(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const r
                int band_rows, int first, int step, void* out, size_t frame_bytes, int fmt) {
     return trace_views(ctx, d, stream, W, H, cams, n_frames, t, band_rows, first, step, out, frame_bytes, fmt, nullptr, 0);
 }
-// n_frames frames from track frame first_frame on, frame j with cams[j] (check_anim bounds them).
+// n_frames frames of 1 << t sub-frames from track frame first_frame on, sub-frame j with cams[j] (check_anim bounds them).
 int trace_anim(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const rt_camera* cams, int first_frame, int n_frames,
-               int band_rows, int first, int step, void* out, size_t frame_bytes, int fmt) {
-    return trace_views(ctx, d, stream, W, H, cams, n_frames, 0, band_rows, first, step, out, frame_bytes, fmt, &ctx->track,
+               int t, int band_rows, int first, int step, void* out, size_t frame_bytes, int fmt) {
+    return trace_views(ctx, d, stream, W, H, cams, n_frames, t, band_rows, first, step, out, frame_bytes, fmt, &ctx->track,
                        first_frame);
 }
 
@@ -2036,17 +2040,19 @@ int check_path(rt_ctx* ctx, const char* who, int W, int H, const rt_camera* cams
     return check_path_samples(ctx, who, W, H);
 }
 
-// check_path for the scene-track renders: the track stands where the scene does, then the frame range.
-int check_anim(rt_ctx* ctx, const char* who, int W, int H, const rt_camera* cams, int first_frame, int n_frames) {
+// check_path for the scene-track renders: the track stands where the scene does, then the frame range -- n_frames
+// frames of `shutter` track frames each (rt_render_anim_shutter*; the shutter itself is check_shutter's to judge).
+int check_anim(rt_ctx* ctx, const char* who, int W, int H, const rt_camera* cams, int first_frame, int n_frames,
+               int shutter = 1) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "NULL context");
     if (!cams || n_frames <= 0 || n_frames > RT_MAX_PATH_FRAMES)
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: NULL cameras or a frame count outside 1..%d", who, RT_MAX_PATH_FRAMES);
     if (!ctx->has_track) return fail(ctx, RT_ERR_NO_SCENE, "%s: rt_set_scene_track has not been called", who);
     if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31) - 1)
         return fail(ctx, RT_ERR_INVALID_ARG, "invalid frame size %dx%d", W, H);
-    if (first_frame < 0 || (long long)first_frame + n_frames > ctx->track.n_frames)
+    if (first_frame < 0 || (long long)first_frame + (long long)n_frames * shutter > ctx->track.n_frames)
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: frames %d..%lld outside the track's %d", who, first_frame,
-                    (long long)first_frame + n_frames - 1, ctx->track.n_frames);
+                    (long long)first_frame + (long long)n_frames * shutter - 1, ctx->track.n_frames);
     if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s needs a single-GPU context", who);
     if (ctx->ss_log2 > 0)
         return fail(ctx, RT_ERR_UNSUPPORTED, "%s does not supersample under rt_set_supersampling (rt_set_path_supersampling is its factor)", who);
@@ -2075,13 +2081,15 @@ int check_shutter(rt_ctx* ctx, const char* who, int n_frames, int shutter, int* 
 }
 
 // rt_render_path_bands and rt_render_shutter_bands (t = log2 of the shutter) after their argument checks.
-// first_frame >= 0: rt_render_anim_bands, the frames of the context's scene track from that one on.
+// first_frame >= 0: rt_render_anim_bands, the frames of the context's scene track from that one on, and
+// rt_render_anim_shutter_bands with its shutter (t is then its log2, found here: check_anim's refusals come first).
 int path_bands(rt_ctx* ctx, const char* who, int width, int height, const rt_camera* cameras, int n_frames, int t,
                int band_rows, int band_first, int band_step, void* d_out, size_t frame_stride_bytes, int format,
-               void* hip_stream, int* out_n_bands, int first_frame = -1) {
+               void* hip_stream, int* out_n_bands, int first_frame = -1, int anim_shutter = 1) {
     const bool anim = first_frame != -1;
-    RT_TRY(anim ? check_anim(ctx, who, width, height, cameras, first_frame, n_frames)
+    RT_TRY(anim ? check_anim(ctx, who, width, height, cameras, first_frame, n_frames, anim_shutter)
                 : check_path(ctx, who, width, height, cameras, n_frames));
+    if (anim) RT_TRY(check_shutter(ctx, who, n_frames, anim_shutter, &t));
     RT_TRY(check_band_args(ctx, who, band_rows, band_first, band_step, d_out, format));
     RT_TRY(check_path_adaptive_bands(ctx, who, band_rows, height));
     const int nb = bands_of(height, band_rows, band_first, band_step);
@@ -2089,7 +2097,7 @@ int path_bands(rt_ctx* ctx, const char* who, int width, int height, const rt_cam
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: frame stride smaller than a frame's output", who);
     Device& d = ctx->dev[0];
     DeviceGuard guard(d.id);
-    const int rc = anim ? trace_anim(ctx, d, (hipStream_t)hip_stream, width, height, cameras, first_frame, n_frames, band_rows,
+    const int rc = anim ? trace_anim(ctx, d, (hipStream_t)hip_stream, width, height, cameras, first_frame, n_frames, t, band_rows,
                                      band_first, band_step, d_out, frame_stride_bytes, format)
                         : trace_path(ctx, d, (hipStream_t)hip_stream, width, height, cameras, n_frames, t, band_rows, band_first,
                                      band_step, d_out, frame_stride_bytes, format);
@@ -2120,14 +2128,16 @@ int rt_render_shutter_bands(rt_ctx* ctx, int width, int height, const rt_camera*
 // copied out by the copy engine on copy_stream once its trace event has fired, under the trace of chunk c + 1;
 // the trace of chunk c + 2 waits for that copy (the Tick pattern of tick_sync's chunks, over frames).
 // rt_render_path and rt_render_shutter (t = log2 of the shutter: frames, chunks and buffers are output frames, and
-// a chunk's launch takes its chunk << t cameras).
+// a chunk's launch takes its chunk << t cameras).  rt_render_anim_shutter: a chunk of nf output frames from output frame
+// f0 takes its cameras from f0 << t and its track frames from first_frame + (f0 << t).
 namespace {
 int path_frames(rt_ctx* ctx, const char* who, int width, int height, const rt_camera* cameras, int n_frames, int t,
-                int32_t* pixels, int first_frame = -1) {
-    const bool anim = first_frame != -1;  // rt_render_anim: the scene track's frames from that one on
-    int rc = anim ? check_anim(ctx, who, width, height, cameras, first_frame, n_frames)
+                int32_t* pixels, int first_frame = -1, int anim_shutter = 1) {
+    const bool anim = first_frame != -1;  // rt_render_anim[_shutter]: the scene track's frames from that one on
+    int rc = anim ? check_anim(ctx, who, width, height, cameras, first_frame, n_frames, anim_shutter)
                   : check_path(ctx, who, width, height, cameras, n_frames);
     if (rc != RT_OK) return rc;
+    if (anim) RT_TRY(check_shutter(ctx, who, n_frames, anim_shutter, &t));
     if (!pixels) return fail(ctx, RT_ERR_INVALID_ARG, "NULL pixels");
     RT_TRY(wait_pending_async(ctx));
     Device& d = ctx->dev[0];
@@ -2152,8 +2162,8 @@ int path_frames(rt_ctx* ctx, const char* who, int width, int height, const rt_ca
     for (int c = 0; c < n_chunks; ++c) {
         const int f0 = c * chunk, nf = std::min(chunk, n_frames - f0), b = c & 1;
         if (c >= 2 && !hip_ok(hipStreamWaitEvent(d.stream, copied[b], 0), "hipStreamWaitEvent")) break;
-        rc = anim ? trace_anim(ctx, d, d.stream, width, height, cameras + f0, first_frame + f0, nf, height, 0, 1, d.d_path[b],
-                               frame_bytes, RT_BANDS_INT32)
+        rc = anim ? trace_anim(ctx, d, d.stream, width, height, cameras + ((size_t)f0 << t), first_frame + (f0 << t), nf, t, height,
+                               0, 1, d.d_path[b], frame_bytes, RT_BANDS_INT32)
                   : trace_path(ctx, d, d.stream, width, height, cameras + ((size_t)f0 << t), nf, t, height, 0, 1, d.d_path[b],
                                frame_bytes, RT_BANDS_INT32);
         if (rc != RT_OK) break;
@@ -2198,6 +2208,21 @@ int rt_render_anim(rt_ctx* ctx, int width, int height, const rt_camera* cameras,
                    int32_t* pixels) {
     if (first_frame == -1) first_frame = INT_MIN;
     return path_frames(ctx, "rt_render_anim", width, height, cameras, n_frames, 0, pixels, first_frame);
+}
+
+// shutter == 1 is the track call: the same launch, the ANIM kernels.
+int rt_render_anim_shutter_bands(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame, int n_frames,
+                                 int shutter, int band_rows, int band_first, int band_step, void* d_out,
+                                 size_t frame_stride_bytes, int format, void* hip_stream, int* out_n_bands) {
+    if (first_frame == -1) first_frame = INT_MIN;
+    return path_bands(ctx, "rt_render_anim_shutter_bands", width, height, cameras, n_frames, 0, band_rows, band_first, band_step,
+                      d_out, frame_stride_bytes, format, hip_stream, out_n_bands, first_frame, shutter);
+}
+
+int rt_render_anim_shutter(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame, int n_frames,
+                           int shutter, int32_t* pixels) {
+    if (first_frame == -1) first_frame = INT_MIN;
+    return path_frames(ctx, "rt_render_anim_shutter", width, height, cameras, n_frames, 0, pixels, first_frame, shutter);
 }
 
 // Double-buffered Tick() on one in-order stream per worker.  Frame k's band set is traced into device

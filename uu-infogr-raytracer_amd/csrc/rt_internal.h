@@ -316,6 +316,14 @@ struct LaunchParams {
     // material and geometry read through a wave-uniform index; 0: no wave is classified (a zeroed block, and
     // RT_UNIFORM_PLANE=0 through rt_set_scene).  Last: no other field moves.
     int uniform_plane;
+    // Scene-track shutters (rt_render_anim_shutter_bands, the ANIM_SHUTTER / ANIM_SHUTTER_SS instantiations): 1 marks a
+    // launch with `views`, a scene_stride and shutter_log2 > 0 -- a shutter launch whose sub-frame s of grid z, record
+    // rec = z << shutter_log2 | s, takes its view from views[rec] and reads each of the 12 scene tables at its pointer +
+    // rec * scene_stride: the image pointers are those of the launch's first sub-frame and the track's images lie
+    // scene_stride apart, one per sub-frame (rt_kernel.hip SceneOf).  0: a scene_stride with a shutter stays a
+    // combination no kernel is built for (a zeroed block).  In the padding between uniform_plane and
+    // shgrp: no field moves and the block keeps its size.
+    int scene_shutter;
     // The shadow pre-test's group and union records (DevShadowGroups [L]; the direct kernel's plane-uniform waves;
     // culling only), or nullptr: the flat loop over every pair (no pre-test records, RT_SHADOW_GROUPS=0 through
     // rt_set_scene, a zeroed block).  Last: no other field moves.
@@ -369,8 +377,11 @@ enum : int { TV_DIRECT = 0, TV_BUNDLE = 1 };
 // scene image (LaunchParams::scene_stride).  PATH_SS, SHUTTER_SS, ANIM_SS: the twins of PATH, SHUTTER and ANIM whose
 // lanes are samples of the k W x k H frame, with SS's tile mapping and epilogue (LaunchParams::view_ss).  PATH_ADAPT,
 // ANIM_ADAPT: PATH_SS and ANIM_SS launches that decide per output tile as ADAPT does (LaunchParams::view_adapt).
+// ANIM_SHUTTER, ANIM_SHUTTER_SS: SHUTTER and SHUTTER_SS launches whose sub-frames also have their own scene image
+// (LaunchParams::scene_shutter).
 enum : int { TM_PLAIN = 0, TM_STATS = 1, TM_TILES = 2, TM_SS = 3, TM_PATH = 4, TM_SHUTTER = 5, TM_ADAPT = 6, TM_PROG = 7, TM_ANIM = 8,
-             TM_PATH_SS = 9, TM_SHUTTER_SS = 10, TM_ANIM_SS = 11, TM_PATH_ADAPT = 12, TM_ANIM_ADAPT = 13 };
+             TM_PATH_SS = 9, TM_SHUTTER_SS = 10, TM_ANIM_SS = 11, TM_PATH_ADAPT = 12, TM_ANIM_ADAPT = 13, TM_ANIM_SHUTTER = 14,
+             TM_ANIM_SHUTTER_SS = 15 };
 struct TraceVariant {
     int family;  // TV_*
     int gpow;    // some material needs the f64 Math.Pow path: the entry points without the register caps
@@ -390,6 +401,8 @@ constexpr unsigned VF_VIEW_SS = VF_PATH_SS | VF_SHUTTER_SS | VF_ANIM_SS;
 // (the adaptive twins of PATH_SS and ANIM_SS, likewise)
 constexpr unsigned VF_PATH_ADAPT = 1u << 22, VF_ANIM_ADAPT = 1u << 23;
 constexpr unsigned VF_VIEW_ADAPT = VF_PATH_ADAPT | VF_ANIM_ADAPT;
+// (the scene-track twins of SHUTTER and SHUTTER_SS, likewise)
+constexpr unsigned VF_ANIM_SHUTTER = 1u << 24, VF_ANIM_SHUTTER_SS = 1u << 25;
 constexpr unsigned vf_cls(int c) { return (unsigned)c << 8; }
 constexpr unsigned vf_wpg(int w) { return (unsigned)w << 12; }
 constexpr unsigned vf_tord(int t) { return (unsigned)t << 16; }
@@ -403,7 +416,8 @@ constexpr unsigned variant_word(const TraceVariant& v) {
            (v.mode == TM_SHUTTER ? VF_SHUTTER : 0u) | (v.mode == TM_ADAPT ? VF_ADAPT : 0u) | (v.mode == TM_PROG ? VF_PROG : 0u) |
            (v.mode == TM_ANIM ? VF_ANIM : 0u) | (v.mode == TM_PATH_SS ? VF_PATH_SS : 0u) |
            (v.mode == TM_SHUTTER_SS ? VF_SHUTTER_SS : 0u) | (v.mode == TM_ANIM_SS ? VF_ANIM_SS : 0u) |
-           (v.mode == TM_PATH_ADAPT ? VF_PATH_ADAPT : 0u) | (v.mode == TM_ANIM_ADAPT ? VF_ANIM_ADAPT : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
+           (v.mode == TM_PATH_ADAPT ? VF_PATH_ADAPT : 0u) | (v.mode == TM_ANIM_ADAPT ? VF_ANIM_ADAPT : 0u) |
+           (v.mode == TM_ANIM_SHUTTER ? VF_ANIM_SHUTTER : 0u) | (v.mode == TM_ANIM_SHUTTER_SS ? VF_ANIM_SHUTTER_SS : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
 }
 
 // The bundle family's shadow pass by scene: 0 = per light (also every scene of the direct family), 1 = the
@@ -418,8 +432,9 @@ inline int merged_class(int S, int L, bool lights_a2_ok) {
 // 8-row grid when the bands are multiples of 8 output rows, or when one band covers the frame.
 inline bool adaptive_band_ok(int band_rows, int H) { return band_rows % 8 == 0 || band_rows >= H; }
 
-// The instantiations that exist (924): every mode, depth and class of both families at one tile per workgroup
-// in grid order (SHUTTER, ANIM, PATH_SS, SHUTTER_SS, ANIM_SS, PATH_ADAPT and ANIM_ADAPT among them, under PATH's conditions,
+// The instantiations that exist (1044): every mode, depth and class of both families at one tile per workgroup
+// in grid order (SHUTTER, ANIM, PATH_SS, SHUTTER_SS, ANIM_SS, PATH_ADAPT, ANIM_ADAPT, ANIM_SHUTTER and ANIM_SHUTTER_SS among
+// them, under PATH's conditions,
 // and ADAPT and PROG, under SS's: 60 of their own each); the
 // direct kernel's lone-frame workgroups of SINGLE_WPG tiles in each tile order (PLAIN only); the all-lights-ok
 // merged bundle kernel's tile orders (PLAIN, no GPOW).
@@ -436,7 +451,10 @@ inline bool pick_trace_variant(const LaunchParams& p, bool generic_pow, bool sta
     const bool tiles = p.out_fmt == OUT_TILES, ordered = p.tile_order != nullptr || p.tile_cost != nullptr;
     if (p.shutter_log2 != 0 && (p.views == nullptr || p.shutter_log2 < 0 || p.shutter_log2 > 8)) return false;
     // (a scene track: a path launch without a shutter, whose images lie whole 256-byte steps apart)
-    if (p.scene_stride != 0 && (p.views == nullptr || p.shutter_log2 != 0 || p.scene_stride % 256 != 0)) return false;
+    // (scene_shutter = 1: a track under a shutter, one image per sub-frame -- and nothing else carries the mark)
+    if (p.scene_shutter != 0 && (p.scene_shutter != 1 || p.scene_stride == 0 || p.shutter_log2 <= 0 || p.view_adapt != 0)) return false;
+    if (p.scene_stride != 0 && (p.views == nullptr || (p.shutter_log2 != 0 && p.scene_shutter == 0) || p.scene_stride % 256 != 0))
+        return false;
     // (a progressive launch is a supersampling launch of one view, never adaptive)
     if (p.prog_acc != nullptr && (p.views != nullptr || p.ss_log2 <= 0 || p.ss_log2 > 3 || p.adapt_thr != 0 || p.prog_first < 0 ||
                                   p.prog_n < 0 || p.prog_n > 2 || p.prog_first + p.prog_n < 1 ||
@@ -454,6 +472,7 @@ inline bool pick_trace_variant(const LaunchParams& p, bool generic_pow, bool sta
         if ((p.ss_log2 > 0 && p.view_ss == 0) || tiles || stats || ordered || p.copy_z != 0 || p.row_order_n != 0 || p.col_major != 0)
             return false;
         v->mode = p.view_adapt != 0 ? (p.scene_stride != 0 ? TM_ANIM_ADAPT : TM_PATH_ADAPT)
+                  : p.scene_shutter != 0 ? (p.view_ss != 0 ? TM_ANIM_SHUTTER_SS : TM_ANIM_SHUTTER)
                   : p.view_ss != 0 ? (p.shutter_log2 > 0 ? TM_SHUTTER_SS : p.scene_stride != 0 ? TM_ANIM_SS : TM_PATH_SS)
                                  : p.shutter_log2 > 0 ? TM_SHUTTER : p.scene_stride != 0 ? TM_ANIM : TM_PATH;
     } else if (p.ss_log2 > 0) {

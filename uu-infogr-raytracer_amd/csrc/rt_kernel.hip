@@ -40,7 +40,7 @@
 // or slower (C2 +0..16 %, C3 +3..22 %, C4 +16..37 %; profiles/ab/r02_tiles_per_wg_rejected.txt).
 constexpr int WG_THREADS = 64, TILE_W = 8, TILE_H = 8;
 
-// Parts.  The 924 trace instantiations take a quarter of an hour to compile as one translation unit, on one core.  The
+// Parts.  The 1044 trace instantiations take a quarter of an hour to compile as one translation unit, on one core.  The
 // Makefile therefore compiles this file RT_KERNEL_PARTS = 4 times, each time with another RT_KERNEL_PART, in parallel:
 // a part instantiates the trace kernels of its modes only (trace_mode_part) and defines launch_trace_part<its number>;
 // part 0 also holds the kernels that are no templates and every launcher, launch_trace among them, which hands a
@@ -56,10 +56,15 @@ static_assert((RT_KERNEL_PARTS == 1 || RT_KERNEL_PARTS == 4) && RT_KERNEL_PART >
 
 namespace rtk {
 
-// PLAIN, STATS | TILES, SS, PATH, SHUTTER | ADAPT, PROG, ANIM, PATH_SS | SHUTTER_SS, ANIM_SS, PATH_ADAPT, ANIM_ADAPT:
-// 204 + 240 + 240 + 240 instantiations.
-constexpr int trace_mode_part(int mode) { return RT_KERNEL_PARTS == 1 ? 0 : mode < TM_TILES ? 0 : mode < TM_ADAPT ? 1 : mode < TM_SHUTTER_SS ? 2 : 3; }
-static_assert(TM_STATS == 1 && TM_SHUTTER == 5 && TM_PATH_SS == 9 && TM_ANIM_ADAPT == 13, "the modes of each part");
+// PLAIN, STATS | TILES, SS, PATH, SHUTTER | ADAPT, PROG, ANIM, PATH_SS, ANIM_SHUTTER | SHUTTER_SS, ANIM_SS, PATH_ADAPT,
+// ANIM_ADAPT, ANIM_SHUTTER_SS: 204 + 240 + 300 + 300 instantiations.  (Modes come in sixties, so no split of the 1044 has a
+// smaller largest part; parts 0 and 1 -- part 0 is the code object that rt_create loads, with the kernels of every Tick
+// and batch render -- stay what they were.)
+constexpr int trace_mode_part(int mode) {
+    return RT_KERNEL_PARTS == 1 ? 0 : mode == TM_ANIM_SHUTTER ? 2 : mode == TM_ANIM_SHUTTER_SS ? 3 : mode < TM_TILES ? 0 : mode < TM_ADAPT ? 1 : mode < TM_SHUTTER_SS ? 2 : 3;
+}
+static_assert(TM_STATS == 1 && TM_SHUTTER == 5 && TM_PATH_SS == 9 && TM_ANIM_ADAPT == 13 && TM_ANIM_SHUTTER == 14 && TM_ANIM_SHUTTER_SS == 15,
+              "the modes of each part");
 
 // Frame / band output: int32 0x00RRGGBB at the packed band row r (format 0) or at the frame
 // row y (format 2), or packed 24-bit (B, G, R bytes; the top byte of the int32 is always 0)
@@ -243,17 +248,20 @@ __device__ __forceinline__ void encode_tile_fused(const LaunchParams& p, uint32_
 // loads.  The other views never read `rec` (it is a dead constant 0 there: their code is what it was).
 // ANIM (scene tracks, rt_render_anim_bands): PATH's view -- every ViewOf member reads the frame's record exactly as
 // VIEW_PATH does -- in a launch whose frames also have their own scene image (SceneOf below).
-constexpr int VIEW_ARGS = 0, VIEW_PATH = 1, VIEW_SHUTTER = 2, VIEW_ANIM = 3;
+// ANIM_SHUTTER (scene-track shutters, rt_render_anim_shutter_bands): SHUTTER's view -- every ViewOf member reads record
+// `rec` exactly as VIEW_SHUTTER does -- in a launch whose sub-frames also have their own scene image (SceneOf below).
+constexpr int VIEW_ARGS = 0, VIEW_PATH = 1, VIEW_SHUTTER = 2, VIEW_ANIM = 3, VIEW_ANIM_SHUTTER = 4;
 // PATH_SS, SHUTTER_SS, ANIM_SS (rt_set_path_supersampling): the view kind of the twin -- the records are built for the
 // sample frame on the host -- and, independently of it, SS's tile mapping and epilogue (ss_of).
 constexpr int view_of(unsigned V) {
-    return (V & (VF_SHUTTER | VF_SHUTTER_SS)) ? VIEW_SHUTTER
+    return (V & (VF_ANIM_SHUTTER | VF_ANIM_SHUTTER_SS)) ? VIEW_ANIM_SHUTTER
+           : (V & (VF_SHUTTER | VF_SHUTTER_SS)) ? VIEW_SHUTTER
            : (V & (VF_ANIM | VF_ANIM_SS | VF_ANIM_ADAPT)) ? VIEW_ANIM
            : (V & (VF_PATH | VF_PATH_SS | VF_PATH_ADAPT)) ? VIEW_PATH
                                               : VIEW_ARGS;
 }
-constexpr bool ss_of(unsigned V) { return (V & (VF_SS | VF_VIEW_SS)) != 0; }            // a lane is a sample of a k x k block
-constexpr bool shutter_of(unsigned V) { return (V & (VF_SHUTTER | VF_SHUTTER_SS)) != 0; }  // the sub-frame loop stores
+constexpr bool ss_of(unsigned V) { return (V & (VF_SS | VF_VIEW_SS | VF_ANIM_SHUTTER_SS)) != 0; }            // a lane is a sample of a k x k block
+constexpr bool shutter_of(unsigned V) { return (V & (VF_SHUTTER | VF_SHUTTER_SS | VF_ANIM_SHUTTER | VF_ANIM_SHUTTER_SS)) != 0; }  // the sub-frame loop stores
 // PATH_ADAPT, ANIM_ADAPT (rt_set_path_adaptive_sampling): PATH's and ANIM's view and scene reads -- the records built for
 // the sample frame, as for PATH_SS -- with ADAPT's lane mapping (sample_pixel) and decision loop (adaptive_tile).
 constexpr bool adapt_of(unsigned V) { return (V & (VF_ADAPT | VF_VIEW_ADAPT)) != 0; }  // a lane is an output pixel, rec the pass
@@ -261,7 +269,7 @@ template <int PATH>
 struct ViewOf {
     const LaunchParams& p;
     int rec = 0;
-    __device__ __forceinline__ const DevView& v() const { return p.views[PATH == VIEW_SHUTTER ? (unsigned)rec : blockIdx.z]; }
+    __device__ __forceinline__ const DevView& v() const { return p.views[PATH == VIEW_SHUTTER || PATH == VIEW_ANIM_SHUTTER ? (unsigned)rec : blockIdx.z]; }
     __device__ __forceinline__ f3 cam() const {
         if constexpr (PATH != VIEW_ARGS) return mk(v().cam[0], v().cam[1], v().cam[2]);
         else return mk(p.cam[0], p.cam[1], p.cam[2]);
@@ -324,30 +332,37 @@ struct ViewOf {
 // a short-circuit chain moved the class-0 bundle kernels' SGPR spills by up to 15).  The kind travels as the PATH
 // parameter that ViewOf takes; the functions that read the scene have no default for it, so no call can fall back to
 // the launch's image.
+// ANIM_SHUTTER (a scene track under a shutter: one scene image per sub-frame): the table of sub-frame `rec` = z <<
+// shutter_log2 | s is the launch's pointer + rec * scene_stride.  `rec` is the value ViewOf takes, made of blockIdx.z, a
+// kernarg and shutter_tile's wave-uniform loop counter, so the address stays scalar arithmetic and the reads scalar
+// loads; it reaches every function that reads a scene table as a parameter without a default, and every accessor takes
+// it.  The other kinds never read it: for them it is a dead argument of inlined functions (in the ADAPT and PROG
+// kernels the sample pass travels in it, as it does for ViewOf).
 template <int PATH>
 struct SceneOf {
     template <bool NULLABLE, typename T>
-    static __device__ __forceinline__ const T* at(const LaunchParams& p, const T* q) {
-        if constexpr (PATH == VIEW_ANIM) {
-            const T* z = (const T*)((const char*)q + (size_t)blockIdx.z * (size_t)p.scene_stride);
+    static __device__ __forceinline__ const T* at(const LaunchParams& p, const T* q, int rec) {
+        if constexpr (PATH == VIEW_ANIM || PATH == VIEW_ANIM_SHUTTER) {
+            const size_t i = PATH == VIEW_ANIM_SHUTTER ? (size_t)(unsigned)rec : (size_t)blockIdx.z;
+            const T* z = (const T*)((const char*)q + i * (size_t)p.scene_stride);
             if constexpr (NULLABLE) return q == nullptr ? nullptr : z;
             else return z;
         } else {
             return q;
         }
     }
-    static __device__ __forceinline__ const DevSphere* sph(const LaunchParams& p) { return at<false>(p, p.sph); }
-    static __device__ __forceinline__ const DevMaterial* mat(const LaunchParams& p) { return at<false>(p, p.mat); }
-    static __device__ __forceinline__ const DevPlane* pl(const LaunchParams& p) { return at<false>(p, p.pl); }
-    static __device__ __forceinline__ const DevLight* li(const LaunchParams& p) { return at<false>(p, p.li); }
-    static __device__ __forceinline__ const DevSphereCull* scull(const LaunchParams& p) { return at<false>(p, p.scull); }
-    static __device__ __forceinline__ const DevShadowCull* shcull(const LaunchParams& p) { return at<true>(p, p.shcull); }
-    static __device__ __forceinline__ const DevShadowCull* shpre(const LaunchParams& p) { return at<true>(p, p.shpre); }
-    static __device__ __forceinline__ const DevShadowGrid* shg(const LaunchParams& p) { return at<true>(p, p.shg); }
-    static __device__ __forceinline__ const unsigned long long* shgrid(const LaunchParams& p) { return at<true>(p, p.shgrid); }
-    static __device__ __forceinline__ const unsigned long long* shslab(const LaunchParams& p) { return at<true>(p, p.shslab); }
-    static __device__ __forceinline__ const DevCluster* clus(const LaunchParams& p) { return at<true>(p, p.clus); }
-    static __device__ __forceinline__ const DevShadowGroups* shgrp(const LaunchParams& p) { return at<true>(p, p.shgrp); }
+    static __device__ __forceinline__ const DevSphere* sph(const LaunchParams& p, int rec) { return at<false>(p, p.sph, rec); }
+    static __device__ __forceinline__ const DevMaterial* mat(const LaunchParams& p, int rec) { return at<false>(p, p.mat, rec); }
+    static __device__ __forceinline__ const DevPlane* pl(const LaunchParams& p, int rec) { return at<false>(p, p.pl, rec); }
+    static __device__ __forceinline__ const DevLight* li(const LaunchParams& p, int rec) { return at<false>(p, p.li, rec); }
+    static __device__ __forceinline__ const DevSphereCull* scull(const LaunchParams& p, int rec) { return at<false>(p, p.scull, rec); }
+    static __device__ __forceinline__ const DevShadowCull* shcull(const LaunchParams& p, int rec) { return at<true>(p, p.shcull, rec); }
+    static __device__ __forceinline__ const DevShadowCull* shpre(const LaunchParams& p, int rec) { return at<true>(p, p.shpre, rec); }
+    static __device__ __forceinline__ const DevShadowGrid* shg(const LaunchParams& p, int rec) { return at<true>(p, p.shg, rec); }
+    static __device__ __forceinline__ const unsigned long long* shgrid(const LaunchParams& p, int rec) { return at<true>(p, p.shgrid, rec); }
+    static __device__ __forceinline__ const unsigned long long* shslab(const LaunchParams& p, int rec) { return at<true>(p, p.shslab, rec); }
+    static __device__ __forceinline__ const DevCluster* clus(const LaunchParams& p, int rec) { return at<true>(p, p.clus, rec); }
+    static __device__ __forceinline__ const DevShadowGroups* shgrp(const LaunchParams& p, int rec) { return at<true>(p, p.shgrp, rec); }
 };
 
 // Deep-recursion stack (recursion limits >= 8): whole records {hit point, t} and {incoming
@@ -383,14 +398,14 @@ struct ScratchStack {
 // segment.  The walks and the compact stacks' re-walk share it, so the re-walk reproduces
 // every hit point and direction bit for bit.
 template <int PATH>
-__device__ __forceinline__ f3 reflect_at(const LaunchParams& p, f3 o, f3& d, float t, int code) {
+__device__ __forceinline__ f3 reflect_at(const LaunchParams& p, f3 o, f3& d, float t, int code, int rec) {
     const f3 hp = add(o, scale(d, t));
     f3 normal;
     if (code >= 0) {
-        const DevSphere& s = SceneOf<PATH>::sph(p)[code];
+        const DevSphere& s = SceneOf<PATH>::sph(p, rec)[code];
         normal = normalize(sub(hp, mk(s.cx, s.cy, s.cz)));
     } else {
-        const DevPlane& pl = SceneOf<PATH>::pl(p)[~code];
+        const DevPlane& pl = SceneOf<PATH>::pl(p, rec)[~code];
         normal = mk(pl.nx, pl.ny, pl.nz);
     }
     d = sub(d, scale(normal, 2.0f * dot(d, normal)));
@@ -428,7 +443,7 @@ struct LdsStack {
             if (__builtin_amdgcn_ballot_w64(go) == 0) break;
             if (go) {
                 const float2 tc = lv[j * WG_THREADS + (threadIdx.x & 63)];
-                o = reflect_at<PATH>(p, o, d, tc.x, __float_as_int(tc.y));
+                o = reflect_at<PATH>(p, o, d, tc.x, __float_as_int(tc.y), rec);
             }
         }
         const float2 tk = lv[n * WG_THREADS + (threadIdx.x & 63)];
@@ -689,34 +704,34 @@ __device__ __forceinline__ void for_sphere_pairs(const LaunchParams& p, F body) 
 // The group level on top (a member mask from the three group records, pairs outside it skipped) gained no more on C3
 // and cost the scan without records 0.3 us in spilled SGPRs and serial scalar loads: profiles/ab/r15_shadow_groups.txt.
 template <bool A2OK, bool GROUPS, int PATH, typename T>
-__device__ __forceinline__ bool shadow_scan(const LaunchParams& p, f3 hp, const DevLight& l, int li, T& tl) {
+__device__ __forceinline__ bool shadow_scan(const LaunchParams& p, f3 hp, const DevLight& l, int li, T& tl, int rec) {
     int blk = 0;
-    if (A2OK && SceneOf<PATH>::shpre(p) != nullptr) {  // wave-uniform
+    if (A2OK && SceneOf<PATH>::shpre(p, rec) != nullptr) {  // wave-uniform
         const ShadowPreLane q = shadow_pre_lane(hp.x, hp.y, hp.z, l);
         if constexpr (GROUPS) {
             // wave-uniform: no lane keeps the union of the light's discs -- not blocked, no sphere visited
-            if (SceneOf<PATH>::shgrp(p) != nullptr &&
-                __builtin_amdgcn_ballot_w64(shadow_pre_keep(shadow_pre_widen(q, SHADOW_UNION_WIDEN), SceneOf<PATH>::shgrp(p)[li].uni)) == 0)
+            if (SceneOf<PATH>::shgrp(p, rec) != nullptr &&
+                __builtin_amdgcn_ballot_w64(shadow_pre_keep(shadow_pre_widen(q, SHADOW_UNION_WIDEN), SceneOf<PATH>::shgrp(p, rec)[li].uni)) == 0)
                 return false;
         }
-        const DevShadowCull* e = SceneOf<PATH>::shpre(p) + (size_t)li * (size_t)(p.S + (p.S & 1));
+        const DevShadowCull* e = SceneOf<PATH>::shpre(p, rec) + (size_t)li * (size_t)(p.S + (p.S & 1));
         for_sphere_pairs<T>(p, [&](int i) {
             const DevShadowCull e0 = e[i], e1 = e[i + 1];
             const bool k0 = shadow_pre_keep(q, e0), k1 = shadow_pre_keep(q, e1);
             if (__builtin_amdgcn_ballot_w64(k0) != 0) {  // wave-uniform: some lane's ray may be blocked
                 tl.shadow_sphere(blk == 0);
-                blk = shadow_blocked<A2OK>(hp, l, false, SceneOf<PATH>::sph(p)[i]) ? 1 : blk;
+                blk = shadow_blocked<A2OK>(hp, l, false, SceneOf<PATH>::sph(p, rec)[i]) ? 1 : blk;
             }
             if (__builtin_amdgcn_ballot_w64(k1) != 0) {
                 tl.shadow_sphere(blk == 0);
-                blk = shadow_blocked<A2OK>(hp, l, false, SceneOf<PATH>::sph(p)[i + 1]) ? 1 : blk;
+                blk = shadow_blocked<A2OK>(hp, l, false, SceneOf<PATH>::sph(p, rec)[i + 1]) ? 1 : blk;
             }
         });
         return blk != 0;
     }
     for_sphere_pairs<T>(p, [&](int i) {
         tl.shadow_sphere(blk == 0);
-        const DevSphere s0 = SceneOf<PATH>::sph(p)[i], s1 = SceneOf<PATH>::sph(p)[i + 1];
+        const DevSphere s0 = SceneOf<PATH>::sph(p, rec)[i], s1 = SceneOf<PATH>::sph(p, rec)[i + 1];
         blk = shadow_blocked<A2OK>(hp, l, false, s0) ? 1 : blk;
         tl.shadow_sphere((blk == 0) & (i + 1 < p.S));
         blk = shadow_blocked<A2OK>(hp, l, false, s1) ? 1 : blk;
@@ -726,18 +741,18 @@ __device__ __forceinline__ bool shadow_scan(const LaunchParams& p, f3 hp, const 
 
 template <bool GPOW, bool GROUPS, int PATH, typename T>
 __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere, int prim, f3 hp, f3 d, float t, f3 sec,
-                                           unsigned* n_shadow, T& tl) {
-    const DevMaterial& m = SceneOf<PATH>::mat(p)[is_sphere ? prim : p.S + prim];
+                                           unsigned* n_shadow, T& tl, int rec) {
+    const DevMaterial& m = SceneOf<PATH>::mat(p, rec)[is_sphere ? prim : p.S + prim];
     const uint32_t flags = m.flags;
     f3 normal;
     float tile = 1.0f;
     // A plane hit on a dark square whose light terms are provably +0 (rt_dark.h): the light loop is skipped
     bool dark = false;
     if (is_sphere) {
-        const DevSphere& s = SceneOf<PATH>::sph(p)[prim];
+        const DevSphere& s = SceneOf<PATH>::sph(p, rec)[prim];
         normal = normalize(sub(hp, mk(s.cx, s.cy, s.cz)));  // SpherePhongShading :706
     } else {
-        const DevPlane& pl = SceneOf<PATH>::pl(p)[prim];
+        const DevPlane& pl = SceneOf<PATH>::pl(p, rec)[prim];
         normal = mk(pl.nx, pl.ny, pl.nz);
         // checkerboard, :766-770: ((int)u + (int)v) & 1, unchecked int add
         const float u = dot(mk(pl.e1x, pl.e1y, pl.e1z), hp);
@@ -757,7 +772,7 @@ __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere
         const uint32_t pk = m.pow_kind;
         const float pn = m.n;
         for (int li = 0; li < p.L; ++li) {
-            const DevLight& l = SceneOf<PATH>::li(p)[li];
+            const DevLight& l = SceneOf<PATH>::li(p, rec)[li];
             const bool l_ok = l.a2 > 0.0f && l.a2 < __builtin_inff();  // wave-uniform
             // ShapePhongShading, :665-695 (first: it decides whether the shadow test matters)
             const f3 ldir = normalize(sub(mk(l.px, l.py, l.pz), hp));
@@ -772,7 +787,7 @@ __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere
             bool blocked = false;
             if (shadow_matters(ph, l.intensity, att)) {
                 tl.shadow(true);
-                blocked = l_ok ? shadow_scan<true, GROUPS, PATH>(p, hp, l, li, tl) : shadow_scan<false, false, PATH>(p, hp, l, li, tl);
+                blocked = l_ok ? shadow_scan<true, GROUPS, PATH>(p, hp, l, li, tl, rec) : shadow_scan<false, false, PATH>(p, hp, l, li, tl, rec);
             }
             const float inten = blocked ? 0.0f : l.intensity;
             const float ia = inten * att;
@@ -797,8 +812,8 @@ __device__ __forceinline__ f3 shade_direct(const LaunchParams& p, bool is_sphere
 // level-0 lanes.
 template <int PATH, typename T>
 __device__ __forceinline__ f3 shade_plane_uniform(const LaunchParams& p, int plane, f3 hp, f3 d, float t, f3 sec,
-                                                  unsigned* n_shadow, T& tl) {
-    return shade_direct<false, RT_SHADOW_GROUPS != 0, PATH>(p, false, plane, hp, d, t, sec, n_shadow, tl);
+                                                  unsigned* n_shadow, T& tl, int rec) {
+    return shade_direct<false, RT_SHADOW_GROUPS != 0, PATH>(p, false, plane, hp, d, t, sec, n_shadow, tl, rec);
 }
 
 // Candidate spheres of a wave's primary rays: those whose per-frame screen box (view_params)
@@ -899,7 +914,7 @@ __device__ __forceinline__ TilePixel sample_pixel(const LaunchParams& p, int til
 // still visited in ascending index.
 template <bool PRIMARY, bool A2OK, bool GATED, int PATH, typename T>
 __device__ __forceinline__ void nearest_spheres(const LaunchParams& p, f3 o, f3 d, float a2, float a4, bool a2_ok,
-                                                unsigned long long pmask, float& best_s, int& win_s, T& tl, int rec = 0) {
+                                                unsigned long long pmask, float& best_s, int& win_s, T& tl, int rec) {
     if (PRIMARY && ViewOf<PATH>{p, rec}.prim_const()) {
         // o == camera: oc = cam - c and c = oc.oc - r^2 are the same per frame (:614-619);
         // only the wave's candidate spheres, in ascending order (non-candidates give t <= 0)
@@ -921,7 +936,7 @@ __device__ __forceinline__ void nearest_spheres(const LaunchParams& p, f3 o, f3 
             }
             tl.sphere(true);
             tl.sphere(i + 1 < p.S);
-            const DevSphere s0 = SceneOf<PATH>::sph(p)[i], s1 = SceneOf<PATH>::sph(p)[i + 1];
+            const DevSphere s0 = SceneOf<PATH>::sph(p, rec)[i], s1 = SceneOf<PATH>::sph(p, rec)[i + 1];
             const float t0 = sphere_t<A2OK>(o, d, a2, a4, a2_ok, s0);
             const float t1 = sphere_t<A2OK>(o, d, a2, a4, a2_ok, s1);
             if (PRIMARY) {
@@ -936,8 +951,7 @@ __device__ __forceinline__ void nearest_spheres(const LaunchParams& p, f3 o, f3 
 }
 
 template <bool PRIMARY, bool GATED, int PATH, typename T>
-__device__ __forceinline__ Hit nearest_direct(const LaunchParams& p, f3 o, f3 d, T& tl, unsigned long long pmask = 0,
-                                              int rec = 0) {
+__device__ __forceinline__ Hit nearest_direct(const LaunchParams& p, f3 o, f3 d, T& tl, unsigned long long pmask, int rec) {
     const float a = dot(d, d);
     const float a2 = 2.0f * a, a4 = 4.0f * a;
     const bool a2_ok = a2 > 0.0f && a2 < __builtin_inff();
@@ -951,7 +965,7 @@ __device__ __forceinline__ Hit nearest_direct(const LaunchParams& p, f3 o, f3 d,
     int win_p = -1;
     for (int i = 0; i < p.P; ++i) {
         tl.plane(true);
-        plane_take(o, d, SceneOf<PATH>::pl(p)[i], i, best_p, win_p);  // t > 0 && t < best (:985-991, :819-821)
+        plane_take(o, d, SceneOf<PATH>::pl(p, rec)[i], i, best_p, win_p);  // t > 0 && t < best (:985-991, :819-821)
     }
     if (best_s < best_p) return Hit{best_s, win_s};
     if (win_p >= 0) return Hit{best_p, ~win_p};
@@ -965,12 +979,12 @@ __device__ __forceinline__ Hit nearest_direct(const LaunchParams& p, f3 o, f3 d,
 // so they are not tested.  Returns HIT_NONE (Zero) or the plane hit (One);
 // the walk classifies it exactly as it would the full nearest hit.
 template <int PATH, typename T>
-__device__ __forceinline__ Hit terminal_direct(const LaunchParams& p, f3 o, f3 d, T& tl) {
+__device__ __forceinline__ Hit terminal_direct(const LaunchParams& p, f3 o, f3 d, T& tl, int rec) {
     float best_p = __builtin_inff();
     int win_p = -1;
     for (int i = 0; i < p.P; ++i) {
         tl.plane(true);
-        plane_take(o, d, SceneOf<PATH>::pl(p)[i], i, best_p, win_p);
+        plane_take(o, d, SceneOf<PATH>::pl(p, rec)[i], i, best_p, win_p);
     }
     if (win_p < 0 || !(best_p - 0.01f > 0.0f)) return Hit{0.0f, HIT_NONE};
     const float a = dot(d, d);
@@ -979,9 +993,9 @@ __device__ __forceinline__ Hit terminal_direct(const LaunchParams& p, f3 o, f3 d
     float best_s = __builtin_inff();
     int win_s = -1;
     if (__builtin_amdgcn_ballot_w64(!a2_ok) == 0)
-        nearest_spheres<false, true, false, PATH>(p, o, d, a2, a4, a2_ok, 0, best_s, win_s, tl);
+        nearest_spheres<false, true, false, PATH>(p, o, d, a2, a4, a2_ok, 0, best_s, win_s, tl, rec);
     else
-        nearest_spheres<false, false, false, PATH>(p, o, d, a2, a4, a2_ok, 0, best_s, win_s, tl);
+        nearest_spheres<false, false, false, PATH>(p, o, d, a2, a4, a2_ok, 0, best_s, win_s, tl, rec);
     if (best_s < best_p) return Hit{0.0f, HIT_NONE};  // a sphere is selected: Zero
     return Hit{best_p, ~win_p};
 }
@@ -1018,7 +1032,8 @@ struct TileOut {
 };
 
 // DIRECT path, one 8x8 tile: each lane walks its own chain with per-lane (divergent) control
-// flow.  rec: the sub-frame's view record (SHUTTER, wave-uniform; see ViewOf), or the sample pass (ADAPT, wave-uniform;
+// flow.  rec: the sub-frame's view record (SHUTTER, wave-uniform; see ViewOf; ANIM_SHUTTER: its scene image as well, see
+// SceneOf), or the sample pass (ADAPT, wave-uniform;
 // sample_pixel) -- the ADAPT kernels have the one view of the launch parameters and ViewOf never reads it, and the
 // PATH_ADAPT / ANIM_ADAPT kernels' views read blockIdx.z alone.
 template <int K, unsigned V, bool UNIFORM_OK = true, typename T>
@@ -1075,9 +1090,9 @@ __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int 
                 const f3 hp = add(o, scale(d, h.t));
                 stk.push(make_float4(hp.x, hp.y, hp.z, h.t), make_float4(d.x, d.y, d.z, __int_as_float(h.prim)));
                 const int prim = is_sphere ? h.prim : ~h.prim;
-                const uint32_t flags = SceneOf<PATH>::mat(p)[is_sphere ? prim : p.S + prim].flags;
+                const uint32_t flags = SceneOf<PATH>::mat(p, rec)[is_sphere ? prim : p.S + prim].flags;
                 if (!(flags & MAT_MIRROR)) break;
-                o = reflect_at<PATH>(p, o, d, h.t, h.prim);  // :854, CalculateReflectionRay :718-720
+                o = reflect_at<PATH>(p, o, d, h.t, h.prim, rec);  // :854, CalculateReflectionRay :718-720
                 ++count;
                 ++cnt;
                 // count is the same for every lane still walking: no divergence here
@@ -1086,9 +1101,9 @@ __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int 
                     // (count read from the first active lane: a scalar branch, and the mask stays wave-uniform)
                     unsigned smask = ~0u;
                     if (vw.mbox_n() > 0 && __builtin_amdgcn_readfirstlane(count) == 1) smask = mirror_box_select<PATH>(p, mmask, h.t, h.prim, rec);
-                    h = count > p.limit ? terminal_direct<PATH>(p, o, d, tl) : nearest_direct<false, true, PATH>(p, o, d, tl, smask);
+                    h = count > p.limit ? terminal_direct<PATH>(p, o, d, tl, rec) : nearest_direct<false, true, PATH>(p, o, d, tl, smask, rec);
                 } else {
-                    h = count > p.limit ? terminal_direct<PATH>(p, o, d, tl) : nearest_direct<false, false, PATH>(p, o, d, tl);
+                    h = count > p.limit ? terminal_direct<PATH>(p, o, d, tl, rec) : nearest_direct<false, false, PATH>(p, o, d, tl, 0, rec);
                 }
             }
             // backward fold: every recorded hit is shaded in reverse order; a mirror hit
@@ -1120,14 +1135,14 @@ __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int 
                 const int code = __float_as_int(rb.w);
                 const bool is_s = code >= 0;
                 col = shade_direct<GPOW, false, PATH>(p, is_s, is_s ? code : ~code, mk(ra.x, ra.y, ra.z),
-                                               mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl);
+                                               mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl, rec);
             }
             if constexpr (UNIFORM) {
                 if (floor_n != 0 && stk.n != 0) {  // the level-0 lanes of a plane-uniform wave
                     float4 ra, rb;
                     stk.template level0<PATH>(p, ra, rb, rec);
                     const int plane = ~__builtin_amdgcn_readfirstlane(__float_as_int(rb.w));
-                    col = shade_plane_uniform<PATH>(p, plane, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl);
+                    col = shade_plane_uniform<PATH>(p, plane, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z), ra.w, col, &cnt, tl, rec);
                 }
             }
             px32 = (shift_channel(col.x) << 16) | (shift_channel(col.y) << 8) | shift_channel(col.z);
@@ -1352,8 +1367,11 @@ __device__ __forceinline__ void progressive_tile(const LaunchParams& p, int tile
 // SHUTTER_SS, ANIM_SS: PATH, SHUTTER and ANIM launches on the k W x k H sample frame (LaunchParams::view_ss) -- the
 // twin's view and scene reads with SS's tile mapping and epilogue, which the tile traces take from the word
 // independently (view_of, ss_of); SHUTTER_SS resolves the blocks of the lanes' sub-frame sums.  PATH_ADAPT,
-// ANIM_ADAPT: PATH_SS and ANIM_SS launches whose waves decide per output tile as ADAPT's do (adapt_of).  All eleven of
-// the plain batch variants only (no STATS, no TILES, WPG 1, TORD 0: rt_internal.h trace_variant_built).
+// ANIM_ADAPT: PATH_SS and ANIM_SS launches whose waves decide per output tile as ADAPT's do (adapt_of).  ANIM_SHUTTER,
+// ANIM_SHUTTER_SS: SHUTTER and SHUTTER_SS launches whose sub-frame rec also reads its own scene image, rec * scene_stride
+// bytes behind the launch's (LaunchParams::scene_shutter; the same shutter_tile, the record index reaching SceneOf as it
+// reaches ViewOf).  All thirteen of the plain batch variants only (no STATS, no TILES, WPG 1, TORD 0: rt_internal.h
+// trace_variant_built).
 // The options arrive as one variant word V (rt_internal.h VF_*, vf_cls = SMAX) and are read from it by name.
 template <int K, unsigned V>
 __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
@@ -1538,13 +1556,13 @@ __device__ __forceinline__ Bundle make_bundle(f3 o, f3 d, bool active, bool dir_
 
 // Candidate mask of spheres [base, base+n) (n <= 64) for bundle B.  Converged call.
 template <int PATH>
-__device__ __forceinline__ unsigned long long cull_mask(const LaunchParams& p, const Bundle& B, int base, int n) {
+__device__ __forceinline__ unsigned long long cull_mask(const LaunchParams& p, const Bundle& B, int base, int n, int rec) {
     // branch-free (no exec-mask bookkeeping on the scalar unit): every lane loads and tests, lanes
     // >= n are dropped from the ballot; a sphere is culled only when the bundle allows culling,
     // its record is in range and one of the rules holds (NaN anywhere -> candidate)
     const int lane = threadIdx.x & 63;
     const bool in = lane < n;
-    const DevSphereCull s = SceneOf<PATH>::scull(p)[base + (in ? lane : 0)];
+    const DevSphereCull s = SceneOf<PATH>::scull(p, rec)[base + (in ? lane : 0)];
     const f3 w = sub(mk(s.cx, s.cy, s.cz), B.O);
     const float dc = clen3(w) * (1.0f + 0x1p-20f);
     const float mgn = 0x1p-8f * (dc + B.R);
@@ -1571,14 +1589,14 @@ __device__ __forceinline__ unsigned long long cull_mask(const LaunchParams& p, c
 // (~1 ulp, far inside the margin); the products are fused (culling-only arithmetic: fewer roundings).  A lane whose a = d.d is outside [0.5, 2] or whose origin is not finite
 // keeps every cluster, and a cluster with a NaN R (a member without a usable cull record) is never culled.
 template <int PATH>
-__device__ __forceinline__ unsigned long long cluster_mask(const LaunchParams& p, f3 o, f3 d) {
+__device__ __forceinline__ unsigned long long cluster_mask(const LaunchParams& p, f3 o, f3 d, int rec) {
     const float a = dot(d, d);
     const f3 A = cnormalize(d);
     const float ol = __builtin_fabsf(o.x) + __builtin_fabsf(o.y) + __builtin_fabsf(o.z);
     const bool ok = a >= 0.5f && a <= 2.0f && ol < 0x1p40f;
     unsigned long long m = 0;
     for (int j = 0; j < p.n_clus; ++j) {  // wave-uniform
-        const DevCluster c = SceneOf<PATH>::clus(p)[j];
+        const DevCluster c = SceneOf<PATH>::clus(p, rec)[j];
         const f3 w = sub(mk(c.cx, c.cy, c.cz), o);
         const float dc = (__builtin_fabsf(w.x) + __builtin_fabsf(w.y) + __builtin_fabsf(w.z)) * (1.0f + 0x1p-20f);
         const float mgn = 0x1p-8f * (dc + c.R);
@@ -1645,15 +1663,15 @@ __device__ __forceinline__ ShadowSphere make_shadow_sphere(f3 hp, bool active) {
 // ball S.  Converged call.
 template <int PATH>
 __device__ __forceinline__ unsigned long long shadow_sphere_cull(const LaunchParams& p, const ShadowSphere& S,
-                                                                 const DevLight& l, int li, int base, int n) {
+                                                                 const DevLight& l, int li, int base, int n, int rec) {
     const int lane = threadIdx.x & 63;
     const bool in = lane < n;
-    const bool ok = S.ok && SceneOf<PATH>::shcull(p) != nullptr && l.a >= 0x1p-40f && l.a <= 0x1p40f && l.a2 < __builtin_inff();
+    const bool ok = S.ok && SceneOf<PATH>::shcull(p, rec) != nullptr && l.a >= 0x1p-40f && l.a <= 0x1p40f && l.a2 < __builtin_inff();
     if (!ok) return __builtin_amdgcn_ballot_w64(in);  // (uniform) no culling: every sphere is a candidate
     // O in the light's frame (uniform); branch-free per lane, as cull_mask
     const float ou = dot(S.O, mk(l.ux, l.uy, l.uz)), ov = dot(S.O, mk(l.vx, l.vy, l.vz));
     const float oa = dot(S.O, mk(l.ax, l.ay, l.az));
-    const DevShadowCull c = SceneOf<PATH>::shcull(p)[(size_t)li * (size_t)p.S + (size_t)(base + (in ? lane : 0))];
+    const DevShadowCull c = SceneOf<PATH>::shcull(p, rec)[(size_t)li * (size_t)p.S + (size_t)(base + (in ? lane : 0))];
     const float wu = c.cu - ou, wv = c.cv - ov, wa = c.ca - oa;
     const float dc = __builtin_fabsf(wu) + __builtin_fabsf(wv) + __builtin_fabsf(wa);  // >= |C - O|
     const float mgn = 0x1p-8f * (dc + 3.0f * S.R) + S.omgn;
@@ -1670,7 +1688,7 @@ __device__ __forceinline__ unsigned long long shadow_sphere_cull(const LaunchPar
 template <bool PRIMARY, bool A2OK, int PATH, typename T>
 __device__ __forceinline__ void bundle_candidates(const LaunchParams& p, unsigned long long m, int base, f3 o, f3 d,
                                                   float a2, float a4, bool a2_ok, bool active, float& best_s,
-                                                  int& win_s, T& tl, int rec = 0) {
+                                                  int& win_s, T& tl, int rec) {
     auto test = [&](int i) -> float {
         if (PRIMARY && ViewOf<PATH>{p, rec}.prim_const()) {
             // o == camera: oc = cam - c and c = oc.oc - r^2 are per-frame constants (:614-619)
@@ -1679,7 +1697,7 @@ __device__ __forceinline__ void bundle_candidates(const LaunchParams& p, unsigne
             const float disc = b * b - a4 * pc.c;
             return A2OK ? root_t1(b, disc, a2) : (a2_ok ? root_t1(b, disc, a2) : root_full(b, disc, a2));
         }
-        return sphere_t<A2OK>(o, d, a2, a4, a2_ok, SceneOf<PATH>::sph(p)[i]);
+        return sphere_t<A2OK>(o, d, a2, a4, a2_ok, SceneOf<PATH>::sph(p, rec)[i]);
     };
     auto take = [&](float t, int i) {
         if (PRIMARY) take_primary(t, i, best_s, win_s);
@@ -1712,7 +1730,7 @@ __device__ __forceinline__ void bundle_candidates(const LaunchParams& p, unsigne
 // `planes`: the segment's nearest plane hit when the caller already has it (terminal segments).
 template <bool PRIMARY, int PATH, typename T>
 __device__ __forceinline__ Hit nearest_bundle(const LaunchParams& p, f3 o, f3 d, bool active, T& tl,
-                                              unsigned long long pmask = 0, const Hit* planes = nullptr, int rec = 0) {
+                                              unsigned long long pmask, const Hit* planes, int rec) {
     const unsigned long long am = __builtin_amdgcn_ballot_w64(active);
     if (am == 0) return Hit{0.0f, HIT_NONE};
     // primary segment: the per-frame screen boxes replace the bundle cull
@@ -1740,7 +1758,7 @@ __device__ __forceinline__ Hit nearest_bundle(const LaunchParams& p, f3 o, f3 d,
         // less eagerly measured +2 %).  Wave-uniform.
         // A cone too wide for the bundle cull: the per-lane cluster pre-cull when the scene has clusters (S <= 64).
         const unsigned long long all = n == 64 ? ~0ull : (1ull << n) - 1ull;
-        unsigned long long m = use_box ? pmask : B.ok ? cull_mask<PATH>(p, B, base, n) : p.n_clus ? cluster_mask<PATH>(p, o, d) & all : all;
+        unsigned long long m = use_box ? pmask : B.ok ? cull_mask<PATH>(p, B, base, n, rec) : p.n_clus ? cluster_mask<PATH>(p, o, d, rec) & all : all;
         // candidates in ascending order, selection by selects (take_*, no per-lane branches); the
         // root sequence is chosen once per wave (2a finite-positive on every lane: the usual case)
         if (__builtin_amdgcn_ballot_w64(!a2_ok) == 0)
@@ -1756,7 +1774,7 @@ __device__ __forceinline__ Hit nearest_bundle(const LaunchParams& p, f3 o, f3 d,
     } else {
         for (int i = 0; i < p.P; ++i) {
             tl.plane(active);
-            plane_take(o, d, SceneOf<PATH>::pl(p)[i], i, best_p, win_p);  // t > 0 && t < best
+            plane_take(o, d, SceneOf<PATH>::pl(p, rec)[i], i, best_p, win_p);  // t > 0 && t < best
         }
     }
     if (!active) return Hit{0.0f, HIT_NONE};
@@ -1788,10 +1806,10 @@ __device__ __forceinline__ Hit nearest_bundle(const LaunchParams& p, f3 o, f3 d,
 // margins are shadow_sphere_cull's: 2^-8 (dc + 3R) with dc from the unprojected w, plus 2^-18
 // (|O| + |C|_1) for the rounding of w and of its projections (each < 2^-21 |w|_1, far inside).
 template <int PATH>
-__device__ __forceinline__ unsigned shadow_members_fast(const LaunchParams& p, const ShadowSphere& SS, unsigned want) {
+__device__ __forceinline__ unsigned shadow_members_fast(const LaunchParams& p, const ShadowSphere& SS, unsigned want, int rec) {
     const int lane = threadIdx.x & 63;
     const bool in = lane < p.S;
-    const DevSphereCull c = SceneOf<PATH>::scull(p)[in ? lane : 0];
+    const DevSphereCull c = SceneOf<PATH>::scull(p, rec)[in ? lane : 0];
     const f3 w = sub(mk(c.cx, c.cy, c.cz), SS.O);
     const float dc = (__builtin_fabsf(w.x) + __builtin_fabsf(w.y) + __builtin_fabsf(w.z)) * (1.0f + 0x1p-20f);
     const float c1 = __builtin_fabsf(c.cx) + __builtin_fabsf(c.cy) + __builtin_fabsf(c.cz);
@@ -1799,12 +1817,12 @@ __device__ __forceinline__ unsigned shadow_members_fast(const LaunchParams& p, c
     const float T = SS.R + c.rr + mgn;
     const float T2 = T * T, nb = -(SS.R + mgn);
     // NaN anywhere -> candidate; a ball that allows no culling keeps every sphere
-    const bool valid = SS.ok && SceneOf<PATH>::shcull(p) != nullptr && c.rr >= 0x1p-50f && dc >= 0x1p-30f && dc < 0x1p40f &&
+    const bool valid = SS.ok && SceneOf<PATH>::shcull(p, rec) != nullptr && c.rr >= 0x1p-50f && dc >= 0x1p-30f && dc < 0x1p40f &&
                        c1 < 0x1p40f;
     unsigned memb = 0;
     for (int li = 0; li < p.L; ++li) {
         if (__builtin_amdgcn_ballot_w64((want >> li) & 1u) == 0) continue;  // wave-uniform
-        const DevLight& l = SceneOf<PATH>::li(p)[li];
+        const DevLight& l = SceneOf<PATH>::li(p, rec)[li];
         const bool l_ok = l.a >= 0x1p-40f && l.a <= 0x1p40f && l.a2 < __builtin_inff();  // wave-uniform
         const float wu = __builtin_fmaf(w.z, l.uz, __builtin_fmaf(w.y, l.uy, w.x * l.ux));
         const float wv = __builtin_fmaf(w.z, l.vz, __builtin_fmaf(w.y, l.vy, w.x * l.vx));
@@ -1839,15 +1857,15 @@ constexpr int GRID_FROM_LEVEL = 1;
 // wave 27.4 -> 7.2).  Culling-only arithmetic (FMA allowed; the margins cover the projections'
 // rounding).  Same result layout as shadow_members.  Converged call.
 template <int PATH>
-__device__ __forceinline__ unsigned shadow_members_grid(const LaunchParams& p, f3 hp, unsigned want) {
+__device__ __forceinline__ unsigned shadow_members_grid(const LaunchParams& p, f3 hp, unsigned want, int rec) {
     const int lane = threadIdx.x & 63;
     const float l1 = __builtin_fabsf(hp.x) + __builtin_fabsf(hp.y) + __builtin_fabsf(hp.z);
     unsigned memb = 0;
     for (int li = 0; li < p.L; ++li) {
         const bool w = (want >> li) & 1u;
         if (__builtin_amdgcn_ballot_w64(w) == 0) continue;  // wave-uniform
-        const DevShadowGrid& g = SceneOf<PATH>::shg(p)[li];
-        const DevLight& l = SceneOf<PATH>::li(p)[li];
+        const DevShadowGrid& g = SceneOf<PATH>::shg(p, rec)[li];
+        const DevLight& l = SceneOf<PATH>::li(p, rec)[li];
         const float u = __builtin_fmaf(hp.z, l.uz, __builtin_fmaf(hp.y, l.uy, hp.x * l.ux));
         const float v = __builtin_fmaf(hp.z, l.vz, __builtin_fmaf(hp.y, l.vy, hp.x * l.vx));
         const float a = __builtin_fmaf(hp.z, l.az, __builtin_fmaf(hp.y, l.ay, hp.x * l.ax));
@@ -1858,13 +1876,13 @@ __device__ __forceinline__ unsigned shadow_members_grid(const LaunchParams& p, f
         const bool in_grid = (xu >= 0.0f) & (xu < (float)SHGRID_N) & (xv >= 0.0f) & (xv < (float)SHGRID_N);
         const unsigned iu = (unsigned)__builtin_fminf(__builtin_fmaxf(xu, 0.0f), (float)(SHGRID_N - 1));
         const unsigned iv = (unsigned)__builtin_fminf(__builtin_fmaxf(xv, 0.0f), (float)(SHGRID_N - 1));
-        const unsigned long long cell = SceneOf<PATH>::shgrid(p)[(unsigned)li * (SHGRID_N * SHGRID_N) + iv * SHGRID_N + iu];
+        const unsigned long long cell = SceneOf<PATH>::shgrid(p, rec)[(unsigned)li * (SHGRID_N * SHGRID_N) + iv * SHGRID_N + iu];
         // slab of a (far lanes: lowered by their extra margin); NaN and below the range: entry 0 (all)
         const float mg = g.far_k * l1;
         const float af = near ? a : a - (mg - g.far_b);
         const float xa = __builtin_fminf(__builtin_fmaxf(__builtin_floorf(__builtin_fmaf(af, g.sa, g.oa)), -1.0f),
                                          (float)SHGRID_SLABS);
-        const unsigned long long slab = SceneOf<PATH>::shslab(p)[(unsigned)li * (SHGRID_SLABS + 2) + (unsigned)((int)xa + 1)];
+        const unsigned long long slab = SceneOf<PATH>::shslab(p, rec)[(unsigned)li * (SHGRID_SLABS + 2) + (unsigned)((int)xa + 1)];
         // far lanes: the box of every disc grown by the lane's own margin (NaN: inside)
         const bool out_box = (u < g.bu0 - mg) | (u > g.bu1 + mg) | (v < g.bv0 - mg) | (v > g.bv1 + mg);
         const bool take = w & (near ? in_grid : !out_box);
@@ -1881,14 +1899,14 @@ __device__ __forceinline__ unsigned shadow_members_grid(const LaunchParams& p, f
 // (C4 -0.4 %, C5 -0.4 %, profiles/ab/r05_merged_loop_ab.txt).
 template <bool A2OK, int PATH, typename T>
 __device__ __forceinline__ unsigned shadow_merged(const LaunchParams& p, unsigned memb, f3 hp, unsigned want, bool diff,
-                                                  bool act, T& tl) {
+                                                  bool act, T& tl, int rec) {
     unsigned long long U = __builtin_amdgcn_ballot_w64(memb != 0u);
     unsigned blk = 0;
     while (U) {
         const int i = (int)__builtin_ctzll(U);
         U &= U - 1;
         const unsigned mi = (unsigned)__builtin_amdgcn_readlane((int)memb, i);  // lights with sphere i
-        const DevSphere sp = SceneOf<PATH>::sph(p)[i];
+        const DevSphere sp = SceneOf<PATH>::sph(p, rec)[i];
         const f3 oc = sub(hp, mk(sp.cx, sp.cy, sp.cz));  // shared by the lights (shadow_blocked's oc, c)
         const float c = dot(oc, oc) - sp.r2;
 #pragma unroll
@@ -1898,7 +1916,7 @@ __device__ __forceinline__ unsigned shadow_merged(const LaunchParams& p, unsigne
             if (__builtin_amdgcn_ballot_w64(pending) == 0) continue;  // wave-uniform
             tl.shadow_cat(pending ? 0 : (((want >> li) & 1u) ? 1 : (diff ? 2 : (act ? 3 : 4))), 1u);
             tl.shadow_sphere(pending);
-            const DevLight& l = SceneOf<PATH>::li(p)[li];
+            const DevLight& l = SceneOf<PATH>::li(p, rec)[li];
             const float b = 2.0f * dot(oc, mk(l.px, l.py, l.pz));
             const float disc = b * b - l.a4 * c;
             bool hit = false;
@@ -1927,9 +1945,9 @@ __device__ __forceinline__ unsigned shadow_merged(const LaunchParams& p, unsigne
 // need them form one bundle per light (common direction = the light position).
 template <bool GPOW, int MERGED, int PATH, typename T>
 __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool is_sphere, int prim, f3 hp, f3 d, float t,
-                                           f3 sec, unsigned* n_shadow, T& tl, int level) {
+                                           f3 sec, unsigned* n_shadow, T& tl, int level, int rec) {
     // idle lanes (act false) carry a copy of an active lane's record: same branches, result dropped
-    const DevMaterial& m = SceneOf<PATH>::mat(p)[is_sphere ? prim : p.S + prim];
+    const DevMaterial& m = SceneOf<PATH>::mat(p, rec)[is_sphere ? prim : p.S + prim];
     const uint32_t flags = m.flags;
     const bool diff = act && (flags & MAT_DIFFUSE) != 0;
     // checkerboard, :766-770: ((int)u + (int)v) & 1, unchecked int add -- first, for the dark-tile skip: a
@@ -1938,7 +1956,7 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
     float tile = 1.0f;
     bool dark = false;
     if (!is_sphere) {
-        const DevPlane& pl = SceneOf<PATH>::pl(p)[prim];
+        const DevPlane& pl = SceneOf<PATH>::pl(p, rec)[prim];
         const float u = dot(mk(pl.e1x, pl.e1y, pl.e1z), hp);
         const float v = dot(mk(pl.e2x, pl.e2y, pl.e2z), hp);
         tile = checker_tile(u, v);
@@ -1964,23 +1982,23 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
         // lie within one grid cell of their centre (light 0's cell size), the grid otherwise (C4 -1.3 %,
         // C5 -1.6 % against the grid there, profiles/ab/r04_adaptive_level1.txt).  Wave-uniform choices.
         unsigned memb;
-        if (SceneOf<PATH>::shg(p) && level > GRID_FROM_LEVEL) {
-            memb = shadow_members_grid<PATH>(p, hp, want);
-        } else if (SceneOf<PATH>::shg(p) && level == GRID_FROM_LEVEL) {
+        if (SceneOf<PATH>::shg(p, rec) && level > GRID_FROM_LEVEL) {
+            memb = shadow_members_grid<PATH>(p, hp, want, rec);
+        } else if (SceneOf<PATH>::shg(p, rec) && level == GRID_FROM_LEVEL) {
             const ShadowSphere SS = make_shadow_sphere(hp, lit);
-            const float cell = 1.0f / __builtin_fmaxf(SceneOf<PATH>::shg(p)[0].su, SceneOf<PATH>::shg(p)[0].sv);
-            memb = SS.ok && SS.R < cell ? shadow_members_fast<PATH>(p, SS, want) : shadow_members_grid<PATH>(p, hp, want);
+            const float cell = 1.0f / __builtin_fmaxf(SceneOf<PATH>::shg(p, rec)[0].su, SceneOf<PATH>::shg(p, rec)[0].sv);
+            memb = SS.ok && SS.R < cell ? shadow_members_fast<PATH>(p, SS, want, rec) : shadow_members_grid<PATH>(p, hp, want, rec);
         } else {
-            memb = shadow_members_fast<PATH>(p, make_shadow_sphere(hp, lit), want);
+            memb = shadow_members_fast<PATH>(p, make_shadow_sphere(hp, lit), want, rec);
         }
-        blk = shadow_merged<MERGED == 2, PATH>(p, memb, hp, want, diff, act, tl);
+        blk = shadow_merged<MERGED == 2, PATH>(p, memb, hp, want, diff, act, tl, rec);
     }
     f3 normal;
     if (is_sphere) {
-        const DevSphere& s = SceneOf<PATH>::sph(p)[prim];
+        const DevSphere& s = SceneOf<PATH>::sph(p, rec)[prim];
         normal = normalize(sub(hp, mk(s.cx, s.cy, s.cz)));  // SpherePhongShading :706
     } else {
-        const DevPlane& pl = SceneOf<PATH>::pl(p)[prim];
+        const DevPlane& pl = SceneOf<PATH>::pl(p, rec)[prim];
         normal = mk(pl.nx, pl.ny, pl.nz);
     }
     f3 col = mk(0.0f, 0.0f, 0.0f);
@@ -1997,7 +2015,7 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
         if (MERGED == 0) SS = make_shadow_sphere(hp, lit);  // one bound for every light's shadow rays
         unsigned long long umask = 0;  // (diagnostic builds: the union of the lights' candidates)
         for (int li = 0; li < p.L; ++li) {
-            const DevLight& l = SceneOf<PATH>::li(p)[li];
+            const DevLight& l = SceneOf<PATH>::li(p, rec)[li];
             const f3 lp = mk(l.px, l.py, l.pz);
             const bool l_ok = l.a2 > 0.0f && l.a2 < __builtin_inff();  // wave-uniform
             // ShapePhongShading, :665-695 (first: it decides whether the shadow test matters)
@@ -2020,7 +2038,7 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
                 const f3 hs = need ? hp : SS.O;  // idle lanes mirror a shading lane (results ignored)
                 for (int base = 0; base < p.S; base += 64) {
                     const int n = min(64, p.S - base);
-                    unsigned long long mk64 = shadow_sphere_cull<PATH>(p, SS, l, li, base, n);
+                    unsigned long long mk64 = shadow_sphere_cull<PATH>(p, SS, l, li, base, n, rec);
                     tl.shadow_masks(5, mk64);
                     umask |= mk64;
                     // candidates two at a time: independent tests (ILP across the sqrt chains),
@@ -2032,7 +2050,7 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
                         const bool two = mk64 != 0;
                         const int i1 = two ? base + (int)__builtin_ctzll(mk64) : i0;
                         if (two) mk64 &= mk64 - 1;
-                        const DevSphere s0 = SceneOf<PATH>::sph(p)[i0], s1 = SceneOf<PATH>::sph(p)[i1];
+                        const DevSphere s0 = SceneOf<PATH>::sph(p, rec)[i0], s1 = SceneOf<PATH>::sph(p, rec)[i1];
                         tl.shadow_cat(need ? (blocked ? 1 : 0) : (diff ? 2 : (act ? 3 : 4)), 2u);
                         tl.shadow_sphere(!blocked);
                         const bool h0 = shadow_blocked<false, true>(hs, l, l_ok, s0);
@@ -2065,7 +2083,7 @@ __device__ __forceinline__ f3 shade_bundle(const LaunchParams& p, bool act, bool
 // hit is shaded; a mirror hit consumes the colour of the segment after it (levels 0..limit push
 // at most one record each, so K = limit + 1 records suffice).  Returns the lane's colour.
 template <bool GPOW, int MERGED, int PATH, typename STK, typename T>
-__device__ __forceinline__ f3 fold_converged(const LaunchParams& p, STK& stk, f3 leaf, unsigned* cnt, T& tl, int rec = 0) {
+__device__ __forceinline__ f3 fold_converged(const LaunchParams& p, STK& stk, f3 leaf, unsigned* cnt, T& tl, int rec) {
     f3 col = leaf;
     const int depth = stk.n;
     int level = (int)wave_max((float)depth);
@@ -2089,7 +2107,7 @@ __device__ __forceinline__ f3 fold_converged(const LaunchParams& p, STK& stk, f3
         const bool is_s = code >= 0;
         tl.set_level(level);
         col = shade_bundle<GPOW, MERGED, PATH>(p, act, is_s, is_s ? code : ~code, mk(ra.x, ra.y, ra.z), mk(rb.x, rb.y, rb.z),
-                                         ra.w, col, cnt, tl, level);
+                                         ra.w, col, cnt, tl, level, rec);
     }
     return col;
 }
@@ -2139,11 +2157,11 @@ __device__ __forceinline__ TileOut trace_tile_bundle(const LaunchParams& p, int 
                 const f3 hp = add(o, scale(d, h.t));
                 stk.push(make_float4(hp.x, hp.y, hp.z, h.t), make_float4(d.x, d.y, d.z, __int_as_float(h.prim)));
                 const int prim = is_sphere ? h.prim : ~h.prim;
-                const uint32_t flags = SceneOf<PATH>::mat(p)[is_sphere ? prim : p.S + prim].flags;
+                const uint32_t flags = SceneOf<PATH>::mat(p, rec)[is_sphere ? prim : p.S + prim].flags;
                 if (!(flags & MAT_MIRROR)) {
                     active = false;
                 } else {
-                    o = reflect_at<PATH>(p, o, d, h.t, h.prim);  // :854, CalculateReflectionRay :718-720
+                    o = reflect_at<PATH>(p, o, d, h.t, h.prim, rec);  // :854, CalculateReflectionRay :718-720
                     ++cnt;
                 }
             }
@@ -2156,17 +2174,17 @@ __device__ __forceinline__ TileOut trace_tile_bundle(const LaunchParams& p, int 
             int win_p = -1;
             for (int i = 0; i < p.P; ++i) {
                 tl.plane(active);
-                plane_take(o, d, SceneOf<PATH>::pl(p)[i], i, best_p, win_p);  // t > 0 && t < best
+                plane_take(o, d, SceneOf<PATH>::pl(p, rec)[i], i, best_p, win_p);  // t > 0 && t < best
             }
             const bool need = active && win_p >= 0 && best_p - 0.01f > 0.0f;
             h = Hit{0.0f, HIT_NONE};
             if (__builtin_amdgcn_ballot_w64(need) != 0) {
                 const Hit pl{best_p, win_p};  // (idle lanes: replaced by a copy of an active lane's ray)
-                const Hit hn = nearest_bundle<false, PATH>(p, o, d, need, tl, 0, &pl);
+                const Hit hn = nearest_bundle<false, PATH>(p, o, d, need, tl, 0, &pl, rec);
                 if (need) h = hn;
             }
         } else {
-            h = nearest_bundle<false, PATH>(p, o, d, active, tl);
+            h = nearest_bundle<false, PATH>(p, o, d, active, tl, 0, nullptr, rec);
         }
     }
 
@@ -2263,6 +2281,7 @@ __device__ __forceinline__ void append_segment(DevSegment* out, int cap, unsigne
 __global__ __launch_bounds__(256) void debug_segments_kernel(LaunchParams p, int stride, DevSegment* out, int cap,
                                                              unsigned* count) {
     constexpr int PATH = VIEW_ARGS;  // (the launch's own view and scene image)
+    constexpr int rec = 0;
     const long long idx = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * (long long)stride;
     if (idx >= (long long)p.W * p.H) return;
     const int x = (int)(idx % p.W), y = (int)(idx / p.W);
@@ -2275,7 +2294,7 @@ __global__ __launch_bounds__(256) void debug_segments_kernel(LaunchParams p, int
     f3 d = normalize(sub(vp, cam));
     f3 o = cam;
     Tally<false> tl;
-    Hit h = nearest_direct<true, false, VIEW_ARGS>(p, o, d, tl, p.S >= 64 ? ~0ull : (1ull << p.S) - 1);  // every sphere
+    Hit h = nearest_direct<true, false, VIEW_ARGS>(p, o, d, tl, p.S >= 64 ? ~0ull : (1ull << p.S) - 1, rec);  // every sphere
     for (int level = 0;; ++level) {
         const bool none = h.prim == HIT_NONE;
         append_segment(out, cap, count, o, add(o, scale(d, none ? 100.0f : h.t)), level == 0 ? 0 : 1,
@@ -2284,18 +2303,18 @@ __global__ __launch_bounds__(256) void debug_segments_kernel(LaunchParams p, int
         const bool is_sphere = h.prim >= 0;
         const int prim = is_sphere ? h.prim : ~h.prim;
         const f3 hp = add(o, scale(d, h.t));
-        const DevMaterial& m = SceneOf<PATH>::mat(p)[is_sphere ? prim : p.S + prim];
+        const DevMaterial& m = SceneOf<PATH>::mat(p, rec)[is_sphere ? prim : p.S + prim];
         if (m.flags & MAT_DIFFUSE) {
             for (int li = 0; li < p.L; ++li) {  // IntersectShadowLight's ray per light
-                const DevLight& l = SceneOf<PATH>::li(p)[li];
+                const DevLight& l = SceneOf<PATH>::li(p, rec)[li];
                 const bool l_ok = l.a2 > 0.0f && l.a2 < __builtin_inff();
                 const f3 lp = mk(l.px, l.py, l.pz);
                 float tb = 1.0f;
                 for (int i = 0; i < p.S; ++i) {
-                    if (shadow_blocked<false>(hp, l, l_ok, SceneOf<PATH>::sph(p)[i])) {
-                        const f3 oc = sub(hp, mk(SceneOf<PATH>::sph(p)[i].cx, SceneOf<PATH>::sph(p)[i].cy, SceneOf<PATH>::sph(p)[i].cz));
+                    if (shadow_blocked<false>(hp, l, l_ok, SceneOf<PATH>::sph(p, rec)[i])) {
+                        const f3 oc = sub(hp, mk(SceneOf<PATH>::sph(p, rec)[i].cx, SceneOf<PATH>::sph(p, rec)[i].cy, SceneOf<PATH>::sph(p, rec)[i].cz));
                         const float b = 2.0f * dot(oc, lp);
-                        const float c = dot(oc, oc) - SceneOf<PATH>::sph(p)[i].r2;
+                        const float c = dot(oc, oc) - SceneOf<PATH>::sph(p, rec)[i].r2;
                         const float sq = __builtin_sqrtf(b * b - l.a4 * c);
                         tb = (-b - sq) / l.a2;
                         break;
@@ -2305,11 +2324,11 @@ __global__ __launch_bounds__(256) void debug_segments_kernel(LaunchParams p, int
             }
         }
         if (!(m.flags & MAT_MIRROR)) break;
-        const f3 normal = is_sphere ? normalize(sub(hp, mk(SceneOf<PATH>::sph(p)[prim].cx, SceneOf<PATH>::sph(p)[prim].cy, SceneOf<PATH>::sph(p)[prim].cz)))
-                                    : mk(SceneOf<PATH>::pl(p)[prim].nx, SceneOf<PATH>::pl(p)[prim].ny, SceneOf<PATH>::pl(p)[prim].nz);
+        const f3 normal = is_sphere ? normalize(sub(hp, mk(SceneOf<PATH>::sph(p, rec)[prim].cx, SceneOf<PATH>::sph(p, rec)[prim].cy, SceneOf<PATH>::sph(p, rec)[prim].cz)))
+                                    : mk(SceneOf<PATH>::pl(p, rec)[prim].nx, SceneOf<PATH>::pl(p, rec)[prim].ny, SceneOf<PATH>::pl(p, rec)[prim].nz);
         d = sub(d, scale(normal, 2.0f * dot(d, normal)));
         o = hp;
-        h = nearest_direct<false, false, VIEW_ARGS>(p, o, d, tl);
+        h = nearest_direct<false, false, VIEW_ARGS>(p, o, d, tl, 0, rec);
     }
 }
 
@@ -2361,7 +2380,8 @@ __global__ __launch_bounds__(256) void scatter_gathered_kernel(const unsigned ch
 // in x when col_major is set, or a 1-D grid over the padded tile_order.
 #if RT_KERNEL_PART == 0
 static void trace_grid(const LaunchParams& p, const TraceVariant& v, dim3* grid, dim3* block) {
-    // (ADAPT, PROG, PATH_ADAPT, ANIM_ADAPT: a wave is a tile of output pixels, and W, local_rows are in samples)
+    // (ADAPT, PROG, PATH_ADAPT, ANIM_ADAPT: a wave is a tile of output pixels, and W, local_rows are in samples; in
+    // ANIM_SHUTTER_SS, as in SHUTTER_SS and every other SS twin, a lane is a sample and the grid is in sample tiles)
     const int as = v.mode == TM_ADAPT || v.mode == TM_PROG || v.mode == TM_PATH_ADAPT || v.mode == TM_ANIM_ADAPT ? p.ss_log2 : 0;
     const unsigned tx = (unsigned)(((p.W >> as) + TILE_W - 1) / TILE_W), ty = (unsigned)(((p.local_rows >> as) + TILE_H - 1) / TILE_H);
     const unsigned z = (unsigned)(p.n_frames > 1 ? p.n_frames : 1) + (unsigned)p.copy_z, w = (unsigned)v.wpg;
@@ -2422,7 +2442,7 @@ template <>
 bool launch_trace_part<RT_KERNEL_PART>(const TraceVariant& v, const LaunchParams& p, dim3 grid, dim3 block, hipStream_t s) {
     auto leaf = [&](auto consts) { return launch_built(consts, p, grid, block, s); };
     return peel(leaf, Vals<>{}, v.family, Vals<TV_DIRECT, TV_BUNDLE>{}, v.gpow, Vals<0, 1>{}, v.mode,
-              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT, TM_PROG, TM_ANIM, TM_PATH_SS, TM_SHUTTER_SS, TM_ANIM_SS, TM_PATH_ADAPT, TM_ANIM_ADAPT>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
+              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT, TM_PROG, TM_ANIM, TM_PATH_SS, TM_SHUTTER_SS, TM_ANIM_SS, TM_PATH_ADAPT, TM_ANIM_ADAPT, TM_ANIM_SHUTTER, TM_ANIM_SHUTTER_SS>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
               Vals<1, 2, 4, 6, 8, 64>{}, v.wpg, Vals<1, SINGLE_WPG>{}, v.tord, Vals<0, 1, 2>{});
 }
 

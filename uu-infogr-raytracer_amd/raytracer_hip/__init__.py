@@ -334,6 +334,43 @@ class Context:
         self._check(self.lib.rt_render_shutter(self.ptr, width, height, cams, n, shutter, out.ctypes.data))
         return out.reshape(n, height, width)
 
+    # -- scene-track shutter: m sub-frame scenes and cameras per output frame -----------
+    def _anim_shutter_cameras(self, cameras, shutter, first_frame):
+        cams = self._anim_cameras(cameras, first_frame, None)
+        if shutter < 1 or len(cams) % shutter:
+            raise ValueError(f"{len(cams)} cameras are no multiple of the shutter {shutter}")
+        return cams
+
+    def render_anim_shutter_bands(self, width: int, height: int, cameras, shutter: int, band_rows: int, band_first: int,
+                                  band_step: int, d_ptr: int, frame_stride_bytes: int, fmt: int = abi.RT_BANDS_INT32,
+                                  stream: int = 0, first_frame: int = 0) -> int:
+        """render_shutter_bands over the scene track: len(cameras) / shutter output frames in one launch, frame f the
+        in-kernel round-half-up mean of its `shutter` sub-frames, sub-frame s being track frame first_frame + f *
+        shutter + s seen from cameras[f * shutter + s] (None: each sub-frame scene's own camera, to the track's end),
+        these bands of it at d_ptr + f * frame_stride_bytes (rt_render_anim_shutter_bands).  anim.tween makes the
+        sub-frame scenes of a track (tween(keys, shutter * steps)) and path.subframes the sub-frame cameras of a
+        path; shutter is a power of two up to 256, and a camera count that is no multiple of it a ValueError."""
+        cams = self._anim_shutter_cameras(cameras, shutter, first_frame)
+        nb = C.c_int(0)
+        self._check(self.lib.rt_render_anim_shutter_bands(self.ptr, width, height, cams, first_frame, len(cams) // shutter,
+                                                          shutter, band_rows, band_first, band_step, C.c_void_p(d_ptr),
+                                                          frame_stride_bytes, fmt, C.c_void_p(stream), C.byref(nb)))
+        return nb.value
+
+    def render_anim_shutter(self, cameras=None, width: int = 0, height: int = 0, shutter: int = 1, first_frame: int = 0,
+                            out: np.ndarray | None = None) -> np.ndarray:
+        """Whole output frames of the scene track under a shutter into host memory, [len(cameras) / shutter, height,
+        width] (rt_render_anim_shutter; synchronous): frame f is the mean of its `shutter` sub-frames, each in its own
+        scene (track frame first_frame + f * shutter + s) and camera; cameras None: each sub-frame scene's own camera,
+        to the track's end.  anim.tween and path.subframes make the sub-frame scenes and cameras."""
+        cams = self._anim_shutter_cameras(cameras, shutter, first_frame)
+        n = len(cams) // shutter
+        if out is None:
+            out = np.empty((max(n, 1), height, width), dtype=np.int32)
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.size == max(n, 1) * width * height
+        self._check(self.lib.rt_render_anim_shutter(self.ptr, width, height, cams, first_frame, n, shutter, out.ctypes.data))
+        return out.reshape(n, height, width)
+
     def scatter_gathered(self, width: int, height: int, band_rows: int, world: int, d_gathered: int,
                          rank_stride: int, d_frame: int, fmt: int = abi.RT_BANDS_RGB24, stream: int = 0):
         """Reassemble all ranks' band sets (rank r's at d_gathered + r * rank_stride) into d_frame."""

@@ -159,6 +159,11 @@ EXPORTS = [
     ("rt_render_anim_bands", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     ("rt_render_anim", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_void_p]),
+    ("rt_render_anim_shutter_bands", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int,
+                                               C.c_void_p, C.POINTER(C.c_int)]),
+    ("rt_render_anim_shutter", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p]),
     ("rt_scatter_gathered", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                       C.c_int, C.c_void_p, C.c_void_p]),
     ("rt_wire_layout_of", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(rt_wire_layout)]),
