@@ -285,6 +285,9 @@ int rt_get_adaptive_sampling(const rt_ctx* ctx, int* out_threshold);
  *   - Shutter: shutter == 1 is the path call, as everywhere.  With T > 0, k > 1 and shutter > 1 the two shutter calls
  *     return RT_ERR_UNSUPPORTED, checked with the other shutter arguments, and write nothing: a decision on a mean of
  *     sub-frames needs the sub-frame index and the sample pass side by side in the tile trace, which is not built.
+ *     That refusal is the answer while rt_set_shutter_adaptive_sampling's threshold is 0 (its default): this threshold
+ *     does not cover shutters, and a caller who set only this one learns so instead of paying for full supersampling.
+ *     With the shutter threshold set the shutter calls render adaptively at that threshold and do not consult this one.
  *   - Statistics: frames and pixels count output frames and pixels; with counting on, primary_rays grows by the
  *     traced output pixels x n_frames plus k*k - 1 per valid pixel of every refined tile of every frame, and
  *     reflect_rays / shadow_rays by those samples' rays, every frame counting for itself; with counting off nothing
@@ -294,6 +297,37 @@ int rt_get_adaptive_sampling(const rt_ctx* ctx, int* out_threshold);
  * Returns RT_ERR_INVALID_ARG for a NULL ctx or out pointer, or a threshold outside 0..256. */
 int rt_set_path_adaptive_sampling(rt_ctx* ctx, int threshold);
 int rt_get_path_adaptive_sampling(const rt_ctx* ctx, int* out_threshold);
+/* (ABI 10 addition) Adaptive supersampling for the camera and scene-track shutters: a threshold T of their own, 0 (the
+ * default, off) .. 256.  Only rt_render_shutter[_bands] and rt_render_anim_shutter[_bands] read it, and only at
+ * shutter > 1 with a path factor k > 1 (rt_set_path_supersampling): that is "in effect" below.  At shutter == 1 the
+ * call remains the path or track call, reads rt_set_path_adaptive_sampling and ignores this setting; every other render
+ * ignores it, and rt_set_adaptive_sampling stays ignored by these calls.
+ *   - In effect: the path threshold is not consulted, so there is no refusal -- the call renders adaptively at this
+ *     threshold.  Not in effect (T = 0): the library as it is without this call -- full supersampling of every
+ *     sub-frame when the path threshold is 0, and RT_ERR_UNSUPPORTED when the path threshold is set.
+ *   - Definition, per output frame f of m = shutter sub-frames, each in its own camera (and, for a track, its own
+ *     scene): P_f is the frame the call writes at path factor 1, per channel (sum of the m sub-frames + m / 2) >>
+ *     log2 m; S_f is the frame it writes at factor k with every threshold 0, (sum + m k*k / 2) >> (log2 m + 2 log2 k).
+ *     Tiles are the 8x8 output tiles of the rendered rows; a tile is refined iff it holds two 4-adjacent pixels, both
+ *     inside the tile and the frame, that differ by >= T in an 8-bit channel of P_f; output = S_f on refined tiles, P_f
+ *     elsewhere.  One rounding only, never a mean of means.  Every output frame decides for itself.
+ *   - T = 256 is the factor-1 shutter frame, bit for bit; T = 1 refines every tile whose P_f is not one colour.
+ *   - A wave traces sample (0, 0) of its tile in each of the m sub-frames, decides on their rounded mean with one
+ *     ballot, and traces the other m (k*k - 1) samples only when the tile is refined: nothing extra is traced for the
+ *     decision, and no sub-frame and no sample reaches memory.
+ *   - Bands: while in effect the band calls need band_rows % 8 == 0 or band_rows >= height, else RT_ERR_UNSUPPORTED
+ *     before any device call (where the path threshold's band rule is checked).  Under rt_set_view_height a last tile
+ *     row is cut at the rendered height, and so is its decision.
+ *   - Bounds: shutter * k*k <= RT_MAX_SHUTTER, as without it.
+ *   - Statistics: frames and pixels count output frames and pixels; with counting on, primary_rays grows by the
+ *     traced output pixels x n_frames x m plus m (k*k - 1) per valid pixel of every refined tile, and reflect_rays /
+ *     shadow_rays by those samples' rays, each sub-frame counting in its own view and scene; with counting off
+ *     nothing grows.
+ *   - rt_render_shutter and rt_render_anim_shutter go through the chunk pipeline unchanged: chunks count output
+ *     frames.  Cost: see README "Adaptive shutters".  Single-GPU contexts only, as the calls themselves.
+ * Returns RT_ERR_INVALID_ARG for a NULL ctx or out pointer, or a threshold outside 0..256. */
+int rt_set_shutter_adaptive_sampling(rt_ctx* ctx, int threshold);
+int rt_get_shutter_adaptive_sampling(const rt_ctx* ctx, int* out_threshold);
 /* (ABI 10 addition) Progressive anti-aliasing for a display loop: k = 1 (the default, off), 2, 4 or 8.  While the
  * camera rests, each Tick call -- rt_render, rt_render_async, rt_render_device, and only these -- traces one more
  * sample per pixel and shows the mean so far; when anything of the view changes, the image is the plain frame again.
@@ -435,6 +469,7 @@ int rt_render_path(rt_ctx* ctx, int width, int height, const rt_camera* cameras,
  *     (rt_set_supersampling above 1).
  *   - rt_set_path_supersampling(k) applies: the output is the one round-half-up mean over the shutter's sub-frames
  *     and each pixel's k*k samples, and shutter * k*k must not exceed RT_MAX_SHUTTER (RT_ERR_INVALID_ARG).
+ *     rt_set_shutter_adaptive_sampling(T) then supersamples only the 8x8 tiles whose shutter frame has edges.
  *   - Statistics: frames and pixels count output frames and pixels, launches one per launch; with counting on,
  *     primary_rays grows by the traced pixels x n_frames x shutter and reflect_rays / shadow_rays by the sum
  *     over every sub-frame (each sub-frame counts for itself); with counting off nothing grows.
@@ -495,7 +530,8 @@ int rt_render_anim(rt_ctx* ctx, int width, int height, const rt_camera* cameras,
  *     (log2 m + 2 log2 k) per channel over the m sub-frames and each pixel's k*k samples, and m * k*k must not
  *     exceed RT_MAX_SHUTTER.
  *   - With rt_set_path_adaptive_sampling in effect (a threshold, k > 1) and shutter > 1 the calls return
- *     RT_ERR_UNSUPPORTED and write nothing, as the camera shutter does.
+ *     RT_ERR_UNSUPPORTED and write nothing, as the camera shutter does -- while rt_set_shutter_adaptive_sampling's
+ *     threshold is 0; with it set they render adaptively at that threshold, each sub-frame in its own scene.
  *   - Refusals, each before any device call and in this order.  First those of rt_render_anim*, in their order
  *     above, with the track bound being first_frame + n_frames * shutter <= the track's frames: a NULL context or
  *     cameras, n_frames outside 1..RT_MAX_PATH_FRAMES (RT_ERR_INVALID_ARG); no track (RT_ERR_NO_SCENE); a bad frame

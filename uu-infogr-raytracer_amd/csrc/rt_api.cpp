@@ -286,6 +286,7 @@ struct rt_ctx {
     int adapt_thr = 0;    // rt_set_adaptive_sampling: the threshold T in 1..256 (0: off); in effect while ss_log2 > 0
     int path_ss_log2 = 0; // rt_set_path_supersampling: log2 of the factor of the path, shutter and track renders (0: off)
     int path_adapt_thr = 0;  // rt_set_path_adaptive_sampling: the threshold T in 1..256 of those renders (0: off); in effect while path_ss_log2 > 0
+    int shutter_adapt_thr = 0;  // rt_set_shutter_adaptive_sampling: the threshold T in 1..256 of the shutter renders at shutter > 1 (0: off); in effect while path_ss_log2 > 0
     // rt_set_progressive (rt_progressive.h): log2 of the factor (0: off), the run so far, the c of the last issued
     // Tick frame, and -- only while a Tick call issues its launches -- that Tick's plan (PROG_PLAIN otherwise: band,
     // batch and path renders never see one)
@@ -624,7 +625,8 @@ struct EncTarget {
 // The tail of trace_bands and trace_path: lp launched on `stream` as one of device d's sampled-timing traces
 // (`what` names the caller in the error text), the launch counted and, while the context counts
 // (rt_set_counting), the pixels of rows < H in the nb launched bands (first, step) of n_frames frames; ss:
-// supersampling, so samples -- but one per pixel in an adaptive launch (lp.adapt_thr or lp.view_adapt > 0), whose waves count the
+// supersampling, so samples -- but one per pixel in an adaptive launch (lp.adapt_thr, lp.view_adapt or lp.shutter_adapt > 0; of
+// a shutter launch n_frames counts the sub-frames, so one per pixel and sub-frame), whose waves count the
 // samples they trace beyond that on the device (CNT_EXTRA_PRIMARY, rt_get_stats).  Nothing but the launch lies between the timing events; a caller that probes the
 // dispatch order brackets the whole call with order_begin / order_end.
 int launch_counted(rt_ctx* ctx, Device& d, hipStream_t stream, const LaunchParams& lp, const char* what, int W, int H,
@@ -638,7 +640,7 @@ int launch_counted(rt_ctx* ctx, Device& d, hipStream_t stream, const LaunchParam
     d.stream = saved;
     if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString((hipError_t)e));
     ctx->launches++;
-    if (lp.adapt_thr > 0 || lp.view_adapt > 0) ss = 0;
+    if (lp.adapt_thr > 0 || lp.view_adapt > 0 || lp.shutter_adapt > 0) ss = 0;
     // (a progressive launch: the samples it traces per pixel, none when it only emits)
     const uint64_t per_pixel = lp.prog_acc != nullptr ? (uint64_t)lp.prog_n : (uint64_t)1 << (2 * ss);
     for (int k = 0; k < nb && ctx->counting; ++k) {
@@ -1314,6 +1316,20 @@ int rt_get_path_adaptive_sampling(const rt_ctx* ctx, int* out_threshold) {
     return RT_OK;
 }
 
+int rt_set_shutter_adaptive_sampling(rt_ctx* ctx, int threshold) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_set_shutter_adaptive_sampling: NULL context");
+    if (threshold < 0 || threshold > 256)
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_set_shutter_adaptive_sampling: threshold %d is not in 0..256", threshold);
+    ctx->shutter_adapt_thr = threshold;
+    return RT_OK;
+}
+
+int rt_get_shutter_adaptive_sampling(const rt_ctx* ctx, int* out_threshold) {
+    if (!ctx || !out_threshold) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_get_shutter_adaptive_sampling: NULL argument");
+    *out_threshold = ctx->shutter_adapt_thr;
+    return RT_OK;
+}
+
 int rt_set_progressive(rt_ctx* ctx, int k) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_set_progressive: NULL context");
     const int s = prog_log2(k);
@@ -1920,6 +1936,9 @@ int view_table_fill(rt_ctx* ctx, const rt_camera* cams, int n_views, int W, int 
 // With rt_set_path_adaptive_sampling besides (a threshold, ss > 0, no shutter: check_shutter refuses the combination)
 // LaunchParams::view_adapt selects the PATH_ADAPT / ANIM_ADAPT kernels instead: the same block, records and tables, a grid
 // in output tiles, and the host counts one primary ray per output pixel as for any adaptive launch (launch_counted).
+// With rt_set_shutter_adaptive_sampling in effect (a threshold, ss > 0 and a shutter, t > 0) LaunchParams::shutter_adapt
+// selects the SHUTTER_ADAPT / ANIM_SHUTTER_ADAPT kernels in the same way: SHUTTER_SS's block, records and tables, a grid in
+// output tiles, and the host counts one primary ray per output pixel and sub-frame.  The path threshold is not read.
 int trace_views(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const rt_camera* cams, int n_frames, int t,
                 int band_rows, int first, int step, void* out, size_t frame_bytes, int fmt, const SceneTrack* track,
                 int first_frame) {
@@ -1982,6 +2001,7 @@ int trace_views(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const 
         lp.ss_log2 = ss;
         lp.view_ss = 1;
         if (t == 0) lp.view_adapt = ctx->path_adapt_thr;
+        else lp.shutter_adapt = ctx->shutter_adapt_thr;
     } else {
         lp.band_rows = band_rows, lp.local_rows = nb * band_rows;
     }
@@ -2018,10 +2038,11 @@ int check_path_samples(rt_ctx* ctx, const char* who, int W, int H) {
     return RT_OK;
 }
 
-// rt_set_path_adaptive_sampling in effect (a threshold and a path factor above 1): the band rule of any adaptive launch
-// (rt_internal.h adaptive_band_ok), asked by the band calls before they touch the device.
-int check_path_adaptive_bands(rt_ctx* ctx, const char* who, int band_rows, int H) {
-    if (ctx->path_ss_log2 > 0 && ctx->path_adapt_thr > 0 && !adaptive_band_ok(band_rows, H))
+// rt_set_path_adaptive_sampling in effect (a threshold and a path factor above 1), or, for a call with a shutter above 1
+// (t > 0), rt_set_shutter_adaptive_sampling: the band rule of any adaptive launch (rt_internal.h adaptive_band_ok), asked
+// by the band calls before they touch the device.
+int check_path_adaptive_bands(rt_ctx* ctx, const char* who, int band_rows, int H, int t) {
+    if (ctx->path_ss_log2 > 0 && (t > 0 ? ctx->shutter_adapt_thr : ctx->path_adapt_thr) > 0 && !adaptive_band_ok(band_rows, H))
         return fail(ctx, RT_ERR_UNSUPPORTED,
                     "%s: adaptive sampling needs bands of a multiple of 8 rows, or one band of the whole frame (band_rows %d, height %d)",
                     who, band_rows, H);
@@ -2072,9 +2093,10 @@ int check_shutter(rt_ctx* ctx, const char* who, int n_frames, int shutter, int* 
     if (((long long)shutter << (2 * ctx->path_ss_log2)) > RT_MAX_SHUTTER)
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: shutter %d x path supersampling factor %d squared above %d samples per pixel", who,
                     shutter, 1 << ctx->path_ss_log2, RT_MAX_SHUTTER);
-    // (deciding on a mean of sub-frames needs the sub-frame index and the sample pass side by side in the tile trace)
-    if (shutter > 1 && ctx->path_ss_log2 > 0 && ctx->path_adapt_thr > 0)
-        return fail(ctx, RT_ERR_UNSUPPORTED, "%s: a shutter above 1 is not rendered under rt_set_path_adaptive_sampling with a path supersampling factor above 1", who);
+    // (the path threshold does not cover shutters: rt_set_shutter_adaptive_sampling is theirs, and while it is in effect the
+    // path threshold is not consulted)
+    if (shutter > 1 && ctx->path_ss_log2 > 0 && ctx->path_adapt_thr > 0 && ctx->shutter_adapt_thr == 0)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "%s: a shutter above 1 is not rendered under rt_set_path_adaptive_sampling with a path supersampling factor above 1 (rt_set_shutter_adaptive_sampling is the shutters' threshold)", who);
     *t = 0;
     while ((1 << *t) < shutter) ++*t;
     return RT_OK;
@@ -2091,7 +2113,7 @@ int path_bands(rt_ctx* ctx, const char* who, int width, int height, const rt_cam
                 : check_path(ctx, who, width, height, cameras, n_frames));
     if (anim) RT_TRY(check_shutter(ctx, who, n_frames, anim_shutter, &t));
     RT_TRY(check_band_args(ctx, who, band_rows, band_first, band_step, d_out, format));
-    RT_TRY(check_path_adaptive_bands(ctx, who, band_rows, height));
+    RT_TRY(check_path_adaptive_bands(ctx, who, band_rows, height, t));
     const int nb = bands_of(height, band_rows, band_first, band_step);
     if (n_frames > 1 && frame_stride_bytes < band_output_bytes(width, height, nb, band_rows, format))
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: frame stride smaller than a frame's output", who);

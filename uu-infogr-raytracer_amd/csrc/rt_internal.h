@@ -241,6 +241,14 @@ struct LaunchParams {
     unsigned char* enc_wire;
     uint32_t* enc_stage;
     int enc_tiles_x, enc_tpf, enc_frame0;
+    // Adaptive shutter launches (rt_set_shutter_adaptive_sampling, the SHUTTER_ADAPT / ANIM_SHUTTER_ADAPT instantiations):
+    // the threshold T in 1..256 of a launch with `views`, view_ss = 1, ss_log2 > 0 and shutter_log2 > 0, 0 = none.  With
+    // it set a lane is an output pixel and the grid is in output tiles, as in a PATH_ADAPT launch; the wave traces sample
+    // (0, 0) of its tile in each of the m sub-frames' views (and scenes), decides on the rounded mean of those m pixels,
+    // and traces the other m (k^2 - 1) samples only when the tile is refined (rt_kernel.hip shutter_adaptive_tile).
+    // view_adapt stays refused with a shutter; adapt_thr stays ignored by a launch with `views`.  In the padding between
+    // enc_frame0 and counters: no field moves and the block keeps its size.
+    int shutter_adapt;
     unsigned long long* counters;  // COUNTER_SLOTS x COUNTER_STRIDE (CNT_*)
     // The Tick hand-off fused into a trace launch (rt_render_async: the previous frame; a chunked
     // rt_render: the previous chunk): with copy_z = 1 the launch has one more grid z-slice, z = 0,
@@ -378,10 +386,11 @@ enum : int { TV_DIRECT = 0, TV_BUNDLE = 1 };
 // lanes are samples of the k W x k H frame, with SS's tile mapping and epilogue (LaunchParams::view_ss).  PATH_ADAPT,
 // ANIM_ADAPT: PATH_SS and ANIM_SS launches that decide per output tile as ADAPT does (LaunchParams::view_adapt).
 // ANIM_SHUTTER, ANIM_SHUTTER_SS: SHUTTER and SHUTTER_SS launches whose sub-frames also have their own scene image
-// (LaunchParams::scene_shutter).
+// (LaunchParams::scene_shutter).  SHUTTER_ADAPT, ANIM_SHUTTER_ADAPT: SHUTTER_SS and ANIM_SHUTTER_SS launches that decide
+// per output tile, on the mean of the sub-frames' samples (0, 0), as ADAPT does (LaunchParams::shutter_adapt).
 enum : int { TM_PLAIN = 0, TM_STATS = 1, TM_TILES = 2, TM_SS = 3, TM_PATH = 4, TM_SHUTTER = 5, TM_ADAPT = 6, TM_PROG = 7, TM_ANIM = 8,
              TM_PATH_SS = 9, TM_SHUTTER_SS = 10, TM_ANIM_SS = 11, TM_PATH_ADAPT = 12, TM_ANIM_ADAPT = 13, TM_ANIM_SHUTTER = 14,
-             TM_ANIM_SHUTTER_SS = 15 };
+             TM_ANIM_SHUTTER_SS = 15, TM_SHUTTER_ADAPT = 16, TM_ANIM_SHUTTER_ADAPT = 17 };
 struct TraceVariant {
     int family;  // TV_*
     int gpow;    // some material needs the f64 Math.Pow path: the entry points without the register caps
@@ -403,6 +412,9 @@ constexpr unsigned VF_PATH_ADAPT = 1u << 22, VF_ANIM_ADAPT = 1u << 23;
 constexpr unsigned VF_VIEW_ADAPT = VF_PATH_ADAPT | VF_ANIM_ADAPT;
 // (the scene-track twins of SHUTTER and SHUTTER_SS, likewise)
 constexpr unsigned VF_ANIM_SHUTTER = 1u << 24, VF_ANIM_SHUTTER_SS = 1u << 25;
+// (the adaptive twins of SHUTTER_SS and ANIM_SHUTTER_SS, likewise)
+constexpr unsigned VF_SHUTTER_ADAPT = 1u << 26, VF_ANIM_SHUTTER_ADAPT = 1u << 27;
+constexpr unsigned VF_VIEW_SHUTTER_ADAPT = VF_SHUTTER_ADAPT | VF_ANIM_SHUTTER_ADAPT;
 constexpr unsigned vf_cls(int c) { return (unsigned)c << 8; }
 constexpr unsigned vf_wpg(int w) { return (unsigned)w << 12; }
 constexpr unsigned vf_tord(int t) { return (unsigned)t << 16; }
@@ -417,7 +429,8 @@ constexpr unsigned variant_word(const TraceVariant& v) {
            (v.mode == TM_ANIM ? VF_ANIM : 0u) | (v.mode == TM_PATH_SS ? VF_PATH_SS : 0u) |
            (v.mode == TM_SHUTTER_SS ? VF_SHUTTER_SS : 0u) | (v.mode == TM_ANIM_SS ? VF_ANIM_SS : 0u) |
            (v.mode == TM_PATH_ADAPT ? VF_PATH_ADAPT : 0u) | (v.mode == TM_ANIM_ADAPT ? VF_ANIM_ADAPT : 0u) |
-           (v.mode == TM_ANIM_SHUTTER ? VF_ANIM_SHUTTER : 0u) | (v.mode == TM_ANIM_SHUTTER_SS ? VF_ANIM_SHUTTER_SS : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
+           (v.mode == TM_ANIM_SHUTTER ? VF_ANIM_SHUTTER : 0u) | (v.mode == TM_ANIM_SHUTTER_SS ? VF_ANIM_SHUTTER_SS : 0u) |
+           (v.mode == TM_SHUTTER_ADAPT ? VF_SHUTTER_ADAPT : 0u) | (v.mode == TM_ANIM_SHUTTER_ADAPT ? VF_ANIM_SHUTTER_ADAPT : 0u) | vf_cls(v.cls) | vf_wpg(v.wpg) | vf_tord(v.tord);
 }
 
 // The bundle family's shadow pass by scene: 0 = per light (also every scene of the direct family), 1 = the
@@ -432,9 +445,9 @@ inline int merged_class(int S, int L, bool lights_a2_ok) {
 // 8-row grid when the bands are multiples of 8 output rows, or when one band covers the frame.
 inline bool adaptive_band_ok(int band_rows, int H) { return band_rows % 8 == 0 || band_rows >= H; }
 
-// The instantiations that exist (1044): every mode, depth and class of both families at one tile per workgroup
-// in grid order (SHUTTER, ANIM, PATH_SS, SHUTTER_SS, ANIM_SS, PATH_ADAPT, ANIM_ADAPT, ANIM_SHUTTER and ANIM_SHUTTER_SS among
-// them, under PATH's conditions,
+// The instantiations that exist (1164): every mode, depth and class of both families at one tile per workgroup
+// in grid order (SHUTTER, ANIM, PATH_SS, SHUTTER_SS, ANIM_SS, PATH_ADAPT, ANIM_ADAPT, ANIM_SHUTTER, ANIM_SHUTTER_SS,
+// SHUTTER_ADAPT and ANIM_SHUTTER_ADAPT among them, under PATH's conditions,
 // and ADAPT and PROG, under SS's: 60 of their own each); the
 // direct kernel's lone-frame workgroups of SINGLE_WPG tiles in each tile order (PLAIN only); the all-lights-ok
 // merged bundle kernel's tile orders (PLAIN, no GPOW).
@@ -468,10 +481,16 @@ inline bool pick_trace_variant(const LaunchParams& p, bool generic_pow, bool sta
     if (p.view_adapt != 0 && (p.view_adapt < 1 || p.view_adapt > 256 || p.views == nullptr || p.view_ss != 1 || p.ss_log2 <= 0 ||
                               p.ss_log2 > 3 || p.shutter_log2 != 0))
         return false;
+    // (an adaptive shutter launch: a supersampled shutter launch -- view_ss bounds shutter_log2 + 2 ss_log2 -- and a
+    // threshold; the path threshold stays out of it)
+    if (p.shutter_adapt != 0 && (p.shutter_adapt < 1 || p.shutter_adapt > 256 || p.views == nullptr || p.view_ss != 1 || p.ss_log2 <= 0 ||
+                                 p.ss_log2 > 3 || p.shutter_log2 < 1 || p.shutter_log2 + 2 * p.ss_log2 > 8 || p.view_adapt != 0))
+        return false;
     if (p.views != nullptr) {
         if ((p.ss_log2 > 0 && p.view_ss == 0) || tiles || stats || ordered || p.copy_z != 0 || p.row_order_n != 0 || p.col_major != 0)
             return false;
-        v->mode = p.view_adapt != 0 ? (p.scene_stride != 0 ? TM_ANIM_ADAPT : TM_PATH_ADAPT)
+        v->mode = p.shutter_adapt != 0 ? (p.scene_shutter != 0 ? TM_ANIM_SHUTTER_ADAPT : TM_SHUTTER_ADAPT)
+                  : p.view_adapt != 0 ? (p.scene_stride != 0 ? TM_ANIM_ADAPT : TM_PATH_ADAPT)
                   : p.scene_shutter != 0 ? (p.view_ss != 0 ? TM_ANIM_SHUTTER_SS : TM_ANIM_SHUTTER)
                   : p.view_ss != 0 ? (p.shutter_log2 > 0 ? TM_SHUTTER_SS : p.scene_stride != 0 ? TM_ANIM_SS : TM_PATH_SS)
                                  : p.shutter_log2 > 0 ? TM_SHUTTER : p.scene_stride != 0 ? TM_ANIM : TM_PATH;

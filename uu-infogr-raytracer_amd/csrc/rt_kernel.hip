@@ -40,7 +40,7 @@
 // or slower (C2 +0..16 %, C3 +3..22 %, C4 +16..37 %; profiles/ab/r02_tiles_per_wg_rejected.txt).
 constexpr int WG_THREADS = 64, TILE_W = 8, TILE_H = 8;
 
-// Parts.  The 1044 trace instantiations take a quarter of an hour to compile as one translation unit, on one core.  The
+// Parts.  The 1164 trace instantiations take a quarter of an hour to compile as one translation unit, on one core.  The
 // Makefile therefore compiles this file RT_KERNEL_PARTS = 4 times, each time with another RT_KERNEL_PART, in parallel:
 // a part instantiates the trace kernels of its modes only (trace_mode_part) and defines launch_trace_part<its number>;
 // part 0 also holds the kernels that are no templates and every launcher, launch_trace among them, which hands a
@@ -56,14 +56,15 @@ static_assert((RT_KERNEL_PARTS == 1 || RT_KERNEL_PARTS == 4) && RT_KERNEL_PART >
 
 namespace rtk {
 
-// PLAIN, STATS | TILES, SS, PATH, SHUTTER | ADAPT, PROG, ANIM, PATH_SS, ANIM_SHUTTER | SHUTTER_SS, ANIM_SS, PATH_ADAPT,
-// ANIM_ADAPT, ANIM_SHUTTER_SS: 204 + 240 + 300 + 300 instantiations.  (Modes come in sixties, so no split of the 1044 has a
-// smaller largest part; parts 0 and 1 -- part 0 is the code object that rt_create loads, with the kernels of every Tick
-// and batch render -- stay what they were.)
+// PLAIN, STATS, ANIM_SHUTTER_ADAPT | TILES, SS, PATH, SHUTTER, SHUTTER_ADAPT | ADAPT, PROG, ANIM, PATH_SS, ANIM_SHUTTER |
+// SHUTTER_SS, ANIM_SS, PATH_ADAPT, ANIM_ADAPT, ANIM_SHUTTER_SS: 264 + 300 + 300 + 300 instantiations.  (Modes come in sixties, so
+// no split of the 1164 has a smaller largest part.  Part 0 is the code object that rt_create loads, with the kernels of
+// every Tick and batch render.)
 constexpr int trace_mode_part(int mode) {
-    return RT_KERNEL_PARTS == 1 ? 0 : mode == TM_ANIM_SHUTTER ? 2 : mode == TM_ANIM_SHUTTER_SS ? 3 : mode < TM_TILES ? 0 : mode < TM_ADAPT ? 1 : mode < TM_SHUTTER_SS ? 2 : 3;
+    return RT_KERNEL_PARTS == 1 ? 0 : mode == TM_ANIM_SHUTTER_ADAPT ? 0 : mode == TM_SHUTTER_ADAPT ? 1 : mode == TM_ANIM_SHUTTER ? 2 : mode == TM_ANIM_SHUTTER_SS ? 3 : mode < TM_TILES ? 0 : mode < TM_ADAPT ? 1 : mode < TM_SHUTTER_SS ? 2 : 3;
 }
-static_assert(TM_STATS == 1 && TM_SHUTTER == 5 && TM_PATH_SS == 9 && TM_ANIM_ADAPT == 13 && TM_ANIM_SHUTTER == 14 && TM_ANIM_SHUTTER_SS == 15,
+static_assert(TM_STATS == 1 && TM_SHUTTER == 5 && TM_PATH_SS == 9 && TM_ANIM_ADAPT == 13 && TM_ANIM_SHUTTER == 14 && TM_ANIM_SHUTTER_SS == 15 &&
+                  TM_SHUTTER_ADAPT == 16 && TM_ANIM_SHUTTER_ADAPT == 17,
               "the modes of each part");
 
 // Frame / band output: int32 0x00RRGGBB at the packed band row r (format 0) or at the frame
@@ -254,8 +255,8 @@ constexpr int VIEW_ARGS = 0, VIEW_PATH = 1, VIEW_SHUTTER = 2, VIEW_ANIM = 3, VIE
 // PATH_SS, SHUTTER_SS, ANIM_SS (rt_set_path_supersampling): the view kind of the twin -- the records are built for the
 // sample frame on the host -- and, independently of it, SS's tile mapping and epilogue (ss_of).
 constexpr int view_of(unsigned V) {
-    return (V & (VF_ANIM_SHUTTER | VF_ANIM_SHUTTER_SS)) ? VIEW_ANIM_SHUTTER
-           : (V & (VF_SHUTTER | VF_SHUTTER_SS)) ? VIEW_SHUTTER
+    return (V & (VF_ANIM_SHUTTER | VF_ANIM_SHUTTER_SS | VF_ANIM_SHUTTER_ADAPT)) ? VIEW_ANIM_SHUTTER
+           : (V & (VF_SHUTTER | VF_SHUTTER_SS | VF_SHUTTER_ADAPT)) ? VIEW_SHUTTER
            : (V & (VF_ANIM | VF_ANIM_SS | VF_ANIM_ADAPT)) ? VIEW_ANIM
            : (V & (VF_PATH | VF_PATH_SS | VF_PATH_ADAPT)) ? VIEW_PATH
                                               : VIEW_ARGS;
@@ -264,7 +265,15 @@ constexpr bool ss_of(unsigned V) { return (V & (VF_SS | VF_VIEW_SS | VF_ANIM_SHU
 constexpr bool shutter_of(unsigned V) { return (V & (VF_SHUTTER | VF_SHUTTER_SS | VF_ANIM_SHUTTER | VF_ANIM_SHUTTER_SS)) != 0; }  // the sub-frame loop stores
 // PATH_ADAPT, ANIM_ADAPT (rt_set_path_adaptive_sampling): PATH's and ANIM's view and scene reads -- the records built for
 // the sample frame, as for PATH_SS -- with ADAPT's lane mapping (sample_pixel) and decision loop (adaptive_tile).
-constexpr bool adapt_of(unsigned V) { return (V & (VF_ADAPT | VF_VIEW_ADAPT)) != 0; }  // a lane is an output pixel, rec the pass
+// SHUTTER_ADAPT, ANIM_SHUTTER_ADAPT (rt_set_shutter_adaptive_sampling): SHUTTER's and ANIM_SHUTTER's view and scene reads
+// -- record `rec`, built for the sample frame as for SHUTTER_SS -- with ADAPT's lane mapping, and a decision loop of their
+// own over sub-frames and passes (shutter_adaptive_tile).  The tile trace needs the record index and the sample pass side
+// by side: they arrive packed in its one wave-uniform argument, pass << REC_BITS | rec (n_frames x shutter <=
+// RT_MAX_PATH_FRAMES < 2^16 records, pass < 64), and are split with scalar operations at its top.
+constexpr bool shutter_adapt_of(unsigned V) { return (V & VF_VIEW_SHUTTER_ADAPT) != 0; }
+constexpr bool adapt_of(unsigned V) { return (V & (VF_ADAPT | VF_VIEW_ADAPT | VF_VIEW_SHUTTER_ADAPT)) != 0; }  // a lane is an output pixel, rec the pass
+constexpr int REC_BITS = 16;
+static_assert(RT_MAX_PATH_FRAMES < (1 << REC_BITS), "a shutter launch's record index fits the low bits of the tile trace's argument");
 template <int PATH>
 struct ViewOf {
     const LaunchParams& p;
@@ -1038,15 +1047,17 @@ struct TileOut {
 // PATH_ADAPT / ANIM_ADAPT kernels' views read blockIdx.z alone.
 template <int K, unsigned V, bool UNIFORM_OK = true, typename T>
 __device__ __forceinline__ TileOut trace_tile_direct(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
-                                                     float* stk_dv, T& tl, int rec = 0) {
+                                                     float* stk_dv, T& tl, int recp = 0) {
     constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = ss_of(V), SHUTTER = shutter_of(V);
     constexpr bool ADAPT = adapt_of(V);
     constexpr int PATH = view_of(V);
+    // (SHUTTER_ADAPT: the sample pass above the record index; every other kernel: the one value it had)
+    const int rec = shutter_adapt_of(V) ? recp & ((1 << REC_BITS) - 1) : recp, pass = shutter_adapt_of(V) ? recp >> REC_BITS : recp;
     // plane-uniform waves: not in the GPOW kernels, where a second inlined pow costs an occupancy step, nor where the
     // kernel body says so (UNIFORM_OK)
     constexpr bool UNIFORM = RT_UNIFORM_PLANE && UNIFORM_OK && !GPOW;
     const int lane = threadIdx.x & 63;
-    const TilePixel tpx = ADAPT ? sample_pixel(p, tile_x, tile_y, lane, rec)
+    const TilePixel tpx = ADAPT ? sample_pixel(p, tile_x, tile_y, lane, pass)
                                 : tile_pixel<SS>(p, tile_x * TILE_W + (lane & 7), tile_y * TILE_H + (lane >> 3));
     const int x = tpx.x, r = tpx.r, y = tpx.y;
     const bool valid = tpx.valid;
@@ -1291,6 +1302,76 @@ __device__ __forceinline__ void adaptive_tile(const LaunchParams& p, int tile_x,
     }
 }
 
+// SHUTTER_ADAPT, ANIM_SHUTTER_ADAPT (rt_set_shutter_adaptive_sampling): the wave's tile is 8x8 output pixels of output frame z
+// = blockIdx.z, a lane is one of them, and the frame is the mean of m = 1 << shutter_log2 sub-frames at k x k samples
+// each.  One loop over i = 0 .. m k^2 - 1 in pass-major order -- pass = i >> t, sub-frame s = i & (m - 1) -- calls
+// `trace(p, pass << REC_BITS | rec, tile_x, tile_y)` with the view (and scene) record rec = z << t | s: the first m
+// iterations are sample (0, 0) of every sub-frame, whose rounded mean P (resolve_round_n) is bit for bit the pixel of
+// the shutter frame without supersampling.  After iteration m - 1 the wave decides on P exactly as adaptive_tile does
+// on its pass 0 -- each valid lane against the lanes at -1 and -8, adapt_differs, one ballot -- and a flat tile leaves
+// the loop and stores P.  A refined tile runs the remaining m (k^2 - 1) iterations into the same sums (16-bit fields:
+// m k^2 <= RT_MAX_SHUTTER values) and stores the one rounded mean of all of them: never a mean of means.
+// The loop obeys what shutter_tile and adaptive_tile found: no store and no atomic inside it, ray counts reduced per
+// iteration into scalars and added once after it with the wave's extra samples, the tile position and the kernarg
+// address passed through the empty asm tied to the loop counter, and nothing carried across a trace but the counter,
+// the two sum VGPRs and the wave totals -- the shutter, the factor, the threshold and the counting flag are read again
+// from the launch parameters where they are used.  The loop leaves at i = m - 1 on a flat tile, so i >= m after it
+// says "refined".  Counting follows the views rule: every grid z counts for itself.
+template <typename F>
+__device__ __forceinline__ void shutter_adaptive_tile(const LaunchParams& p, int tile_x, int tile_y, F trace) {
+    ResolveSum acc{0u, 0u};
+    unsigned n_refl = 0;  // (at most 64 lanes x 255 segments x 256 iterations: 32 bits)
+    unsigned long long n_shadow = 0;
+    int i = 0;
+#pragma unroll 1
+    for (;; ++i) {  // wave-uniform
+        int tx = tile_x, ty = tile_y;
+        asm("" : "+s"(tx), "+s"(ty) : "s"(i));
+        const __attribute__((address_space(4))) LaunchParams* kp =
+            (const __attribute__((address_space(4))) LaunchParams*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm("" : "+s"(kp) : "s"(i));
+        const LaunchParams& q = *(const LaunchParams*)kp;
+        const int t = q.shutter_log2, m1 = (1 << t) - 1;
+        const int rec = (int)(blockIdx.z << t) | (i & m1);
+        const TileOut o = trace(q, (i >> t) << REC_BITS | rec, tx, ty);
+        acc = resolve_add(acc, resolve_unpack(o.px32));
+        if (q.counters != nullptr) {  // wave-uniform
+            n_refl += wave_count(o.cnt & CNT_REFL_MASK);
+            n_shadow += wave_count(o.cnt >> CNT_SHADOW_SHIFT);
+        }
+        if (i == m1) {  // the decision, on the shutter frame without supersampling
+            const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            const bool valid = sample_pixel(q, tx, ty, ln, 0).valid;
+            const uint32_t v = resolve_round_n(acc, t);
+            const uint32_t left = row_shr<1>(v);                        // lane - 1: the same row for rx >= 1
+            const uint32_t above = (uint32_t)__shfl_up((int)v, 8, 64);  // lane - 8: the row above
+            const bool differs = valid && (((ln & 7) != 0 && adapt_differs(v, left, q.shutter_adapt)) ||
+                                           ((ln >> 3) != 0 && adapt_differs(v, above, q.shutter_adapt)));
+            if (__builtin_amdgcn_ballot_w64(differs) == 0) break;  // flat
+        }
+        if (i + 1 >= 1 << (t + 2 * q.ss_log2)) break;
+    }
+    const int s2 = p.ss_log2, t = p.shutter_log2;
+    const bool refined = i >= 1 << t;
+    const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const TilePixel px = sample_pixel(p, tile_x, tile_y, ln, 0);  // the pixel's sample (0, 0)
+    if (px.valid)  // (output coordinates: r and y agree modulo k, bands are multiples of k sample rows)
+        store_at(p, (size_t)((p.out_fmt == 2 ? px.y : px.r) >> s2) * (size_t)(p.W >> s2) + (size_t)(px.x >> s2),
+                 resolve_round_n(acc, refined ? t + 2 * s2 : t));
+    if (p.counters != nullptr) {  // wave-uniform
+        // the samples beyond one per pixel and sub-frame: m (k^2 - 1) per valid pixel of a refined tile
+        const unsigned long long n_extra = refined ? (unsigned long long)(((1 << (2 * s2)) - 1) << t) *
+                                                         (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(px.valid))
+                                                   : 0ull;
+        if (ln == 0) {
+            unsigned long long* c = &p.counters[((blockIdx.y * gridDim.x + blockIdx.x) % COUNTER_SLOTS) * COUNTER_STRIDE];
+            if (n_refl) atomicAdd(c + CNT_REFLECT, (unsigned long long)n_refl);
+            if (n_shadow) atomicAdd(c + CNT_SHADOW, n_shadow);
+            if (n_extra) atomicAdd(c + CNT_EXTRA_PRIMARY, n_extra);
+        }
+    }
+}
+
 // PROG (rt_set_progressive, one Tick of a resting camera): the wave's tile is 8x8 output pixels and a lane is one of
 // them, as in an ADAPT launch, and `trace(p, pass, tile_x, tile_y)` traces sample pass = j k + i of every pixel's
 // k x k block.  The launch names 0, 1 or 2 samples (prog_n; their pass codes in prog_pass: the host knows the run's
@@ -1370,8 +1451,9 @@ __device__ __forceinline__ void progressive_tile(const LaunchParams& p, int tile
 // ANIM_ADAPT: PATH_SS and ANIM_SS launches whose waves decide per output tile as ADAPT's do (adapt_of).  ANIM_SHUTTER,
 // ANIM_SHUTTER_SS: SHUTTER and SHUTTER_SS launches whose sub-frame rec also reads its own scene image, rec * scene_stride
 // bytes behind the launch's (LaunchParams::scene_shutter; the same shutter_tile, the record index reaching SceneOf as it
-// reaches ViewOf).  All thirteen of the plain batch variants only (no STATS, no TILES, WPG 1, TORD 0: rt_internal.h
-// trace_variant_built).
+// reaches ViewOf).  SHUTTER_ADAPT, ANIM_SHUTTER_ADAPT: SHUTTER_SS and ANIM_SHUTTER_SS launches whose waves decide per output
+// tile on the mean of the sub-frames (LaunchParams::shutter_adapt, shutter_adaptive_tile).  All fifteen of the plain batch
+// variants only (no STATS, no TILES, WPG 1, TORD 0: rt_internal.h trace_variant_built).
 // The options arrive as one variant word V (rt_internal.h VF_*, vf_cls = SMAX) and are read from it by name.
 template <int K, unsigned V>
 __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
@@ -1413,6 +1495,10 @@ __device__ __forceinline__ void direct_kernel_body(const LaunchParams& p) {
         const bool in = p.tile_cost != nullptr && (unsigned)tile_x < tiles_x && (unsigned)tile_y < tiles_y;
         t_rec[wave] = TileRec{in ? p.tile_cost + ((unsigned)tile_y * tiles_x + (unsigned)tile_x) : nullptr,
                               in ? (unsigned)__builtin_amdgcn_s_memrealtime() : 0u};
+    }
+    if constexpr (shutter_adapt_of(V)) {
+        shutter_adaptive_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int recp, int tx, int ty) { return trace_tile_direct<K, V & VF_TILE>(q, tx, ty, lv, dv, tl, recp); });
+        return;
     }
     if constexpr (SHUTTER) {
         shutter_tile<ss_of(V)>(p, tile_x, tile_y, [&](const LaunchParams& q, int rec, int tx, int ty) { return trace_tile_direct<K, V & VF_TILE>(q, tx, ty, lv, dv, tl, rec); });
@@ -2116,13 +2202,15 @@ __device__ __forceinline__ f3 fold_converged(const LaunchParams& p, STK& stk, f3
 // every segment and every light can form a wave bundle and cull the sphere list.
 template <int K, unsigned V, typename T>
 __device__ __forceinline__ TileOut trace_tile_bundle(const LaunchParams& p, int tile_x, int tile_y, float2* stk_lv,
-                                                     float* stk_dv, T& tl, int rec = 0) {
+                                                     float* stk_dv, T& tl, int recp = 0) {
     constexpr bool GPOW = (V & VF_GPOW) != 0, TILES = (V & VF_TILES) != 0, SS = ss_of(V), SHUTTER = shutter_of(V);
     constexpr bool ADAPT = adapt_of(V);
     constexpr int PATH = view_of(V);
     constexpr int MERGED = vf_cls_of(V);
+    // (SHUTTER_ADAPT: the sample pass above the record index, as in trace_tile_direct)
+    const int rec = shutter_adapt_of(V) ? recp & ((1 << REC_BITS) - 1) : recp, pass = shutter_adapt_of(V) ? recp >> REC_BITS : recp;
     const int lane = threadIdx.x & 63;
-    const TilePixel tpx = ADAPT ? sample_pixel(p, tile_x, tile_y, lane, rec)
+    const TilePixel tpx = ADAPT ? sample_pixel(p, tile_x, tile_y, lane, pass)
                                 : tile_pixel<SS>(p, tile_x * TILE_W + (lane & 7), tile_y * TILE_H + (lane >> 3));
     const int x = tpx.x, y = tpx.y;
     const bool valid = tpx.valid;
@@ -2238,6 +2326,10 @@ __device__ __forceinline__ void bundle_kernel_body(const LaunchParams& p) {
     if (TORD == 2 && (threadIdx.x & 63) == 0)  // (a batch launch's frame 0 records; the others store nothing)
         t_rec[0] = TileRec{blockIdx.z == (unsigned)p.copy_z ? p.tile_cost + (blockIdx.y * gridDim.x + blockIdx.x) : nullptr,
                            (unsigned)__builtin_amdgcn_s_memrealtime()};
+    if constexpr (shutter_adapt_of(V)) {
+        shutter_adaptive_tile(p, tile_x, tile_y, [&](const LaunchParams& q, int recp, int tx, int ty) { return trace_tile_bundle<K, V & VF_TILE>(q, tx, ty, stk_lv, stk_dv, tl, recp); });
+        return;
+    }
     if constexpr (SHUTTER) {
         shutter_tile<ss_of(V)>(p, tile_x, tile_y, [&](const LaunchParams& q, int rec, int tx, int ty) { return trace_tile_bundle<K, V & VF_TILE>(q, tx, ty, stk_lv, stk_dv, tl, rec); });
         return;
@@ -2382,7 +2474,10 @@ __global__ __launch_bounds__(256) void scatter_gathered_kernel(const unsigned ch
 static void trace_grid(const LaunchParams& p, const TraceVariant& v, dim3* grid, dim3* block) {
     // (ADAPT, PROG, PATH_ADAPT, ANIM_ADAPT: a wave is a tile of output pixels, and W, local_rows are in samples; in
     // ANIM_SHUTTER_SS, as in SHUTTER_SS and every other SS twin, a lane is a sample and the grid is in sample tiles)
-    const int as = v.mode == TM_ADAPT || v.mode == TM_PROG || v.mode == TM_PATH_ADAPT || v.mode == TM_ANIM_ADAPT ? p.ss_log2 : 0;
+    const int as = v.mode == TM_ADAPT || v.mode == TM_PROG || v.mode == TM_PATH_ADAPT || v.mode == TM_ANIM_ADAPT ||
+                           v.mode == TM_SHUTTER_ADAPT || v.mode == TM_ANIM_SHUTTER_ADAPT
+                       ? p.ss_log2
+                       : 0;
     const unsigned tx = (unsigned)(((p.W >> as) + TILE_W - 1) / TILE_W), ty = (unsigned)(((p.local_rows >> as) + TILE_H - 1) / TILE_H);
     const unsigned z = (unsigned)(p.n_frames > 1 ? p.n_frames : 1) + (unsigned)p.copy_z, w = (unsigned)v.wpg;
     const unsigned gxw = (tx + w - 1) / w;
@@ -2442,7 +2537,7 @@ template <>
 bool launch_trace_part<RT_KERNEL_PART>(const TraceVariant& v, const LaunchParams& p, dim3 grid, dim3 block, hipStream_t s) {
     auto leaf = [&](auto consts) { return launch_built(consts, p, grid, block, s); };
     return peel(leaf, Vals<>{}, v.family, Vals<TV_DIRECT, TV_BUNDLE>{}, v.gpow, Vals<0, 1>{}, v.mode,
-              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT, TM_PROG, TM_ANIM, TM_PATH_SS, TM_SHUTTER_SS, TM_ANIM_SS, TM_PATH_ADAPT, TM_ANIM_ADAPT, TM_ANIM_SHUTTER, TM_ANIM_SHUTTER_SS>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
+              Vals<TM_PLAIN, TM_STATS, TM_TILES, TM_SS, TM_PATH, TM_SHUTTER, TM_ADAPT, TM_PROG, TM_ANIM, TM_PATH_SS, TM_SHUTTER_SS, TM_ANIM_SS, TM_PATH_ADAPT, TM_ANIM_ADAPT, TM_ANIM_SHUTTER, TM_ANIM_SHUTTER_SS, TM_SHUTTER_ADAPT, TM_ANIM_SHUTTER_ADAPT>{}, v.cls, Vals<0, 1, 2, DIRECT_SMAX>{}, v.K,
               Vals<1, 2, 4, 6, 8, 64>{}, v.wpg, Vals<1, SINGLE_WPG>{}, v.tord, Vals<0, 1, 2>{});
 }
 

@@ -176,6 +176,19 @@ class Context:
         self._check(self.lib.rt_get_path_adaptive_sampling(self.ptr, C.byref(t)))
         return t.value
 
+    def set_shutter_adaptive_sampling(self, threshold: int):
+        """rt_set_shutter_adaptive_sampling: the adaptive threshold (0 = off, the default, .. 256) of render_shutter[_bands]
+        and render_anim_shutter[_bands] at a shutter above 1 and a path supersampling factor above 1: per output frame,
+        only the 8x8 output tiles whose factor-1 shutter frame has pixels that differ by >= threshold are supersampled
+        (supersample.shutter_adaptive_resolve is the definition).  While it is in effect the path threshold is not
+        consulted; at shutter 1 the calls read the path threshold, and every other render ignores this one."""
+        self._check(self.lib.rt_set_shutter_adaptive_sampling(self.ptr, int(threshold)))
+
+    def get_shutter_adaptive_sampling(self) -> int:
+        t = C.c_int(-1)
+        self._check(self.lib.rt_get_shutter_adaptive_sampling(self.ptr, C.byref(t)))
+        return t.value
+
     def set_progressive(self, k: int):
         """rt_set_progressive: k = 1 (off), 2, 4 or 8.  While the view rests, every Tick call (render, render_async,
         render_device) adds a sample per pixel in supersample.progressive_order(k) and returns the mean so far

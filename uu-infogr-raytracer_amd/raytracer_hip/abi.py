@@ -127,6 +127,8 @@ EXPORTS = [
     ("rt_get_adaptive_sampling", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("rt_set_path_adaptive_sampling", C.c_int, [C.c_void_p, C.c_int]),
     ("rt_get_path_adaptive_sampling", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("rt_set_shutter_adaptive_sampling", C.c_int, [C.c_void_p, C.c_int]),
+    ("rt_get_shutter_adaptive_sampling", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("rt_set_progressive", C.c_int, [C.c_void_p, C.c_int]),
     ("rt_get_progressive", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("rt_reset_progressive", C.c_int, [C.c_void_p]),

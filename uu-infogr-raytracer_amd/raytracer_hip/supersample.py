@@ -118,6 +118,35 @@ def path_adaptive_resolve(plain_frames: np.ndarray, sample_frames: np.ndarray, k
     return out
 
 
+def shutter_adaptive_resolve(plain_subframes: np.ndarray, sample_subframes: np.ndarray, k: int, m: int,
+                             threshold: int) -> np.ndarray:
+    """The definition of rt_set_shutter_adaptive_sampling: `plain_subframes` [F * m, H, W] (sub-frame s of output frame
+    f at f * m + s, at path factor 1) and `sample_subframes` [F * m, k H, k W] (the same cameras, and scenes, at k W x
+    k H) -> int32 [F, H, W].  P = path.shutter_mean(plain_subframes, m) is the factor-1 shutter frame and S =
+    path_resolve(sample_subframes, k, m) the fully supersampled one, each with its one rounding; output frame f is S_f
+    on the tiles refine_mask(P_f, threshold) picks and P_f elsewhere: every output frame decides for itself, on the
+    mean of its sub-frames.  threshold 0 (off): S."""
+    from .path import shutter_mean
+    p, s = np.asarray(plain_subframes), np.asarray(sample_subframes)
+    if p.ndim != 3 or s.ndim != 3 or p.shape[0] != s.shape[0]:
+        raise ValueError(f"plain sub-frames {p.shape} and sample sub-frames {s.shape} are no [F m, H, W] and [F m, k H, k W]")
+    if not 0 <= int(threshold) <= 256:
+        raise ValueError(f"adaptive threshold {threshold} is not in 0..256")
+    if k not in FACTORS:
+        raise ValueError(f"supersampling factor {k} is not one of {FACTORS}")
+    if s.shape[1:] != (p.shape[1] * k, p.shape[2] * k):
+        raise ValueError(f"plain sub-frames {p.shape} do not match the sample sub-frames {s.shape} at factor {k}")
+    full = path_resolve(s, k, m)  # (checks m: a power of two with m k k <= 256, and F * m frames)
+    if int(threshold) == 0:
+        return full
+    plain = shutter_mean(p, m)
+    out = np.empty(plain.shape, dtype=np.int32)
+    for f in range(plain.shape[0]):
+        px = np.repeat(np.repeat(refine_mask(plain[f], threshold), TILE, axis=0), TILE, axis=1)[:plain.shape[1], :plain.shape[2]]
+        out[f] = np.where(px, full[f], plain[f])
+    return out
+
+
 # Progressive accumulation (rt_set_progressive): a resting camera's Ticks take the k x k samples of a pixel one by
 # one, coarse sub-grids first, and show the rounded mean of the samples so far.
 def progressive_order(k: int) -> list:
