@@ -671,6 +671,61 @@ typedef struct rt_segment {
 int rt_debug_segments(rt_ctx* ctx, int width, int height, int sample_stride, rt_segment* out,
                       int capacity, int* out_count);
 
+/* ---- hit buffers and picking (ABI 10 additions) -------------------------------- */
+/* What a pixel sees besides its colour: per pixel, the hit that the primary ray selects by TracePixel's rule
+ * (RayTracer.cs:973-993: the nearest sphere with t > 0 in scene order, the nearest plane likewise, the sphere iff
+ * its t is below the plane's).  Written by a primary-only kernel -- no shading, no shadow ray, no reflection.
+ *   depth     the selected primitive's IntersectResult.distance t            | nothing selected: +inf
+ *   object    sphere i -> i, plane j -> n_spheres + j                        | RT_HIT_NONE
+ *   position  origin + direction * t                                         | origin + direction * 100 (as
+ *                                                                              rt_debug_segments' segment end)
+ *   normal    sphere: Normalize(position - center); plane: its normal as set | (0, 0, 0)
+ * The values are bit for bit the reference's binary32 ones.  A selected hit with t - 0.01 <= 0, which the colour
+ * frame renders black (:731, :839), is still the selected hit and is reported like any other.
+ *   - The buffers are those of the plain frame's rays: rt_set_supersampling, rt_set_path_supersampling, every
+ *     adaptive threshold and rt_set_progressive are ignored (sample (0, 0) of each block, as rt_debug_segments), and a
+ *     hit call leaves a progressive run as it is.  rt_set_view_height applies exactly as to rt_render_device.
+ *   - Hit calls add nothing to rt_get_stats (no frames, pixels, launches or rays), do not read rt_set_counting and
+ *     never involve the lone-frame tuner (rt_dispatch_order).
+ *   - Any channel pointer may be NULL: that channel is not written.  All NULL, or a NULL rt_hit_buffers:
+ *     RT_ERR_INVALID_ARG.  Each channel is [n_frames][height][width], frame f at element f * width * height.
+ *   - rt_render_hits_device: the context's camera and scene, asynchronous on hip_stream.  rt_render_path_hits_device:
+ *     frame f seen from cameras[f], as rt_render_path_bands -- ONE launch; cameras, n_frames and the frame size are
+ *     checked as there, `cameras` is consumed before the call returns and the context's camera is neither read nor
+ *     changed.  rt_render_anim_hits_device: frame f is track frame first_frame + f seen from cameras[f], as
+ *     rt_render_anim_bands, with its checks of cameras, n_frames, first_frame and the track.
+ *   - rt_render_hits, rt_render_path_hits, rt_render_anim_hits: the same into host memory, synchronous.  They trace
+ *     into a context-owned device buffer in chunks of as many frames as keep it at or below 256 MiB (at least one)
+ *     and copy each chunk out before the next; rt_destroy releases the buffer.
+ *   - rt_pick: the four values the buffers hold at pixel (x, y) of the context camera's width x height frame, from a
+ *     one-wave launch and a 32-byte copy.  Synchronous.  x or y outside the frame: RT_ERR_INVALID_ARG.
+ *   - Contexts with more than one worker (RT_CREATE_SHARED_DEVICE ones included) return RT_ERR_UNSUPPORTED before any
+ *     device call. */
+#define RT_HIT_NONE (-1)
+typedef struct rt_hit_buffers {
+    float*   depth;
+    int32_t* object;
+    rt_vec3* position;
+    rt_vec3* normal;
+} rt_hit_buffers;
+typedef struct rt_pick_result {
+    int32_t object;
+    float depth;
+    rt_vec3 position;
+    rt_vec3 normal;
+} rt_pick_result;
+int rt_render_hits_device(rt_ctx* ctx, int width, int height, const rt_hit_buffers* d_out, void* hip_stream);
+int rt_render_path_hits_device(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames,
+                               const rt_hit_buffers* d_out, void* hip_stream);
+int rt_render_anim_hits_device(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame,
+                               int n_frames, const rt_hit_buffers* d_out, void* hip_stream);
+int rt_render_hits(rt_ctx* ctx, int width, int height, const rt_hit_buffers* out);
+int rt_render_path_hits(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames,
+                        const rt_hit_buffers* out);
+int rt_render_anim_hits(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame, int n_frames,
+                        const rt_hit_buffers* out);
+int rt_pick(rt_ctx* ctx, int width, int height, int x, int y, rt_pick_result* out);
+
 /* ---- statistics ------------------------------------------------------------- */
 /* Synchronises the context's pending work, then returns the counters. */
 /* Device timing of trace launches, copies and gathers with HIP event pairs: every

@@ -52,6 +52,9 @@ internal static class Native {
     [DllImport(Lib)] internal static extern int rt_set_progressive(IntPtr ctx, int k);  // ABI 10 addition
     [DllImport(Lib)] internal static extern int rt_get_progressive(IntPtr ctx, out int k, out int samples);
     [DllImport(Lib)] internal static extern int rt_reset_progressive(IntPtr ctx);
+    // ABI 10 addition: what a pixel sees (Object: sphere i -> i, plane j -> n_spheres + j, -1 = nothing; Depth +inf then)
+    [StructLayout(LayoutKind.Sequential)] internal struct PickResult { public int Object; public float Depth; public Vec3 Position, Normal; }
+    [DllImport(Lib)] internal static extern int rt_pick(IntPtr ctx, int w, int h, int x, int y, out PickResult result);
 
     internal static void Check(int rc, IntPtr ctx) {
         if (rc != 0) throw new InvalidOperationException($"libraytracer_hip error {rc}: {Marshal.PtrToStringAnsi(rt_last_error(ctx))}");
@@ -115,6 +118,14 @@ internal sealed class RayTracer : IDisposable {
     public void Tick() {                                  // RayTracer.cs:886-935
         Native.Check(Native.rt_set_camera(_ctx, ref _camera), _ctx);
         Native.Check(Native.rt_render(_ctx, screen.width, screen.height, _pin.AddrOfPinnedObject()), _ctx);
+    }
+
+    // What the window's pixel (x, y) sees from the current camera: the object under a click, its distance, the hit
+    // point and the surface normal (one small launch, not a frame; Object -1: nothing).
+    public Native.PickResult Pick(int x, int y) {
+        Native.Check(Native.rt_set_camera(_ctx, ref _camera), _ctx);
+        Native.Check(Native.rt_pick(_ctx, screen.width, screen.height, x, y, out Native.PickResult r), _ctx);
+        return r;
     }
 
     public void OnKeyPress(KeyboardKeyEventArgs e) {      // RayTracer.cs:543-554

@@ -195,6 +195,11 @@ struct Device {
     // rt_set_scene_track: the track's scene images, back to back (worker 0 only: the anim renders are single-worker)
     void* d_track = nullptr;
     size_t track_cap = 0;
+    // rt_render_hits / _path_hits / _anim_hits: a chunk's requested channels, one after the other (hits_host);
+    // rt_pick: its one record
+    void* d_hits = nullptr;
+    size_t hits_cap = 0;
+    DevPick* d_pick = nullptr;
     float* d_view_tab = nullptr;  // lx[W] then ly[H] (view_tables)
     size_t view_tab_cap = 0;
     int tab_w = -1, tab_h = -1;
@@ -1131,6 +1136,8 @@ void rt_destroy(rt_ctx* ctx) {
         if (d.d_counters_diag) (void)hipFree(d.d_counters_diag);
         if (d.d_view_tab) (void)hipFree(d.d_view_tab);
         if (d.d_prog) (void)hipFree(d.d_prog);
+        if (d.d_hits) (void)hipFree(d.d_hits);
+        if (d.d_pick) (void)hipFree(d.d_pick);
         if (d.order.tiles.d_order) (void)hipFree(d.order.tiles.d_order);
         if (d.order.tiles.d_cost) (void)hipFree(d.order.tiles.d_cost);
         if (d.d_stage) (void)hipFree(d.d_stage);
@@ -1912,6 +1919,34 @@ int view_table_fill(rt_ctx* ctx, const rt_camera* cams, int n_views, int W, int 
     return RT_OK;
 }
 
+// The next table slot of the ring, free and with room for n_views records (trace_views states the rules).
+int path_slot_take(rt_ctx* ctx, Device& d, int n_views, Device::PathSlot** out) {
+    Device::PathSlot& ps = d.path_slot[d.path_next++ % Device::PATH_SLOTS];
+    if (ps.busy) {  // the slot's last launch may still read its records
+        HIP_TRY(ctx, hipEventSynchronize(ps.done));
+        ps.busy = false;
+    }
+    RT_TRY(ensure_event(ctx, &ps.done));
+    // (a slot keeps its buffers for the next call, but no more than PATH_SLOT_KEEP records of them: a call that
+    // needs fewer finds a larger table shrunk to its own size, so one long path does not pin its tables for good)
+    if (ps.cap < (size_t)n_views || (ps.cap > Device::PATH_SLOT_KEEP && (size_t)n_views <= Device::PATH_SLOT_KEEP)) {
+        if (ps.h_views) (void)hipHostFree(ps.h_views);
+        if (ps.d_views) (void)hipFree(ps.d_views);
+        ps.h_views = nullptr, ps.d_views = nullptr, ps.cap = 0;
+        const size_t bytes = (size_t)n_views * sizeof(DevView);
+        hipError_t e = hipHostMalloc((void**)&ps.h_views, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void**)&ps.d_views, bytes);
+        if (e != hipSuccess) {
+            if (ps.h_views) (void)hipHostFree(ps.h_views);
+            ps.h_views = nullptr;
+            return fail(ctx, RT_ERR_OOM, "view table of %d frames: %s", n_views, hipGetErrorString(e));
+        }
+        ps.cap = (size_t)n_views;
+    }
+    *out = &ps;
+    return RT_OK;
+}
+
 // The launch of a camera-path call: n_frames frames (grid z), frame f with the view of cams[f].  The views are
 // built on the host by view_fill -- the code behind every one-camera launch -- packed as DevView records into
 // a table slot's pinned staging buffer and uploaded on `stream` ahead of the launch.  The context's camera and
@@ -1946,28 +1981,9 @@ int trace_views(rt_ctx* ctx, Device& d, hipStream_t stream, int W, int H, const 
     const int VH = ctx->view_height > 0 ? ctx->view_height : H;
     const int ss = ctx->path_ss_log2;  // (check_path / check_anim bounded the sample frame, check_shutter m k^2)
     if (H > VH) return fail(ctx, RT_ERR_INVALID_ARG, "frame height %d above the view height %d", H, ctx->view_height);
-    Device::PathSlot& ps = d.path_slot[d.path_next++ % Device::PATH_SLOTS];
-    if (ps.busy) {  // the slot's last launch may still read its records
-        HIP_TRY(ctx, hipEventSynchronize(ps.done));
-        ps.busy = false;
-    }
-    RT_TRY(ensure_event(ctx, &ps.done));
-    // (a slot keeps its buffers for the next call, but no more than PATH_SLOT_KEEP records of them: a call that
-    // needs fewer finds a larger table shrunk to its own size, so one long path does not pin its tables for good)
-    if (ps.cap < (size_t)n_views || (ps.cap > Device::PATH_SLOT_KEEP && (size_t)n_views <= Device::PATH_SLOT_KEEP)) {
-        if (ps.h_views) (void)hipHostFree(ps.h_views);
-        if (ps.d_views) (void)hipFree(ps.d_views);
-        ps.h_views = nullptr, ps.d_views = nullptr, ps.cap = 0;
-        const size_t bytes = (size_t)n_views * sizeof(DevView);
-        hipError_t e = hipHostMalloc((void**)&ps.h_views, bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void**)&ps.d_views, bytes);
-        if (e != hipSuccess) {
-            if (ps.h_views) (void)hipHostFree(ps.h_views);
-            ps.h_views = nullptr;
-            return fail(ctx, RT_ERR_OOM, "view table of %d frames: %s", n_views, hipGetErrorString(e));
-        }
-        ps.cap = (size_t)n_views;
-    }
+    Device::PathSlot* slot = nullptr;
+    RT_TRY(path_slot_take(ctx, d, n_views, &slot));
+    Device::PathSlot& ps = *slot;
     LaunchParams lp;
     std::memset(&lp, 0, sizeof lp);
     int rc = RT_OK;
@@ -2245,6 +2261,177 @@ int rt_render_anim_shutter(rt_ctx* ctx, int width, int height, const rt_camera* 
                            int shutter, int32_t* pixels) {
     if (first_frame == -1) first_frame = INT_MIN;
     return path_frames(ctx, "rt_render_anim_shutter", width, height, cameras, n_frames, 0, pixels, first_frame, shutter);
+}
+
+// ----------------------------------------------------------------------------
+// Hit buffers and picking (include/raytracer_hip.h): the primary-only kernel (rt_kernel.hip hits_kernel) over the
+// context's view, a camera path's or a scene track's.  Apart from every render's bookkeeping: no statistics, no
+// timing samples, no Tick scope (a progressive run stays as it is), no view cache and so no dispatch tuner -- the view
+// is built afresh by view_fill, a few microseconds of host trig per call.  The supersampling factors are not read: the
+// records and the view tables are those of the plain W x VH frame.
+// ----------------------------------------------------------------------------
+namespace {
+enum : int { HITS_CTX = 0, HITS_PATH = 1, HITS_ANIM = 2 };
+
+// The refusals of the seven hit calls, each before any device call: a NULL context; more than one worker; then what
+// check_path (HITS_PATH) or check_anim (HITS_ANIM) ask of cameras, n_frames, the scene or the track, the frame size
+// and first_frame, in their order.
+int check_hits(rt_ctx* ctx, const char* who, int kind, int W, int H, const rt_camera* cams, int first_frame, int n_frames) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "NULL context");
+    if (ctx->n_gpus != 1) return fail(ctx, RT_ERR_UNSUPPORTED, "%s needs a context with one worker", who);
+    if (kind != HITS_CTX && (!cams || n_frames <= 0 || n_frames > RT_MAX_PATH_FRAMES))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: NULL cameras or a frame count outside 1..%d", who, RT_MAX_PATH_FRAMES);
+    if (kind != HITS_ANIM) return check_ctx(ctx, W, H, false);
+    if (!ctx->has_track) return fail(ctx, RT_ERR_NO_SCENE, "%s: rt_set_scene_track has not been called", who);
+    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31) - 1)
+        return fail(ctx, RT_ERR_INVALID_ARG, "invalid frame size %dx%d", W, H);
+    if (first_frame < 0 || (long long)first_frame + (long long)n_frames > ctx->track.n_frames)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: frames %d..%lld outside the track's %d", who, first_frame,
+                    (long long)first_frame + (long long)n_frames - 1, ctx->track.n_frames);
+    return RT_OK;
+}
+int check_hit_buffers(rt_ctx* ctx, const char* who, const rt_hit_buffers* out) {
+    if (!out || (!out->depth && !out->object && !out->position && !out->normal))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: NULL hit buffers, or no channel asked for", who);
+    return RT_OK;
+}
+
+// One hit launch on `stream`: n_frames frames of W x H into `out`.  HITS_CTX: the context's camera (cams unused,
+// n_frames 1).  HITS_PATH / HITS_ANIM: frame j from cams[j] -- and from track frame first_frame + j -- with the views
+// built, staged and uploaded as trace_views does it, through the same ring of table slots.
+int hits_launch(rt_ctx* ctx, Device& d, hipStream_t stream, int kind, int W, int H, const rt_camera* cams, int first_frame,
+                int n_frames, const HitOut& out) {
+    const int VH = ctx->view_height > 0 ? ctx->view_height : H;
+    if (H > VH) return fail(ctx, RT_ERR_INVALID_ARG, "frame height %d above the view height %d", H, ctx->view_height);
+    const SceneTrack* track = kind == HITS_ANIM ? &ctx->track : nullptr;
+    LaunchParams lp;
+    std::memset(&lp, 0, sizeof lp);
+    Device::PathSlot* ps = nullptr;
+    if (kind == HITS_CTX) {
+        RT_TRY(view_fill(ctx, ctx->cam, W, VH, lp));
+    } else {
+        RT_TRY(path_slot_take(ctx, d, n_frames, &ps));
+        for (int j = 0; j < n_frames; ++j) {
+            RT_TRY(view_fill(ctx, track ? track->frames[(size_t)(first_frame + j)] : ctx->layout, cams[j], W, VH, lp));
+            view_record(lp, ps->h_views[j]);
+        }
+    }
+    lp.H = H;  // the rows traced
+    if (track) {
+        scene_params(ctx, d, lp, track->common, (const char*)d.d_track + (size_t)first_frame * track->stride);
+        lp.scene_stride = track->stride;
+    } else {
+        scene_params(ctx, d, lp);
+    }
+    lp.counters = nullptr;  // (the kernel counts nothing)
+    RT_TRY(view_tables(ctx, d, lp));
+    if (ps) {
+        HIP_TRY(ctx, hipMemcpyAsync(ps->d_views, ps->h_views, (size_t)n_frames * sizeof(DevView), hipMemcpyHostToDevice, stream));
+        lp.views = ps->d_views;
+    }
+    lp.band_rows = H, lp.band_first = 0, lp.band_step = 1, lp.local_rows = H;  // one band: local row r is frame row r
+    lp.n_frames = n_frames;
+    const int e = launch_hits(lp, out, stream);
+    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "hit launch: %s", hipGetErrorString((hipError_t)e));
+    if (ps) {
+        HIP_TRY(ctx, hipEventRecord(ps->done, stream));
+        ps->busy = true;
+    }
+    return RT_OK;
+}
+
+int hits_device(rt_ctx* ctx, const char* who, int kind, int W, int H, const rt_camera* cams, int first_frame, int n_frames,
+                const rt_hit_buffers* d_out, void* hip_stream) {
+    RT_TRY(check_hits(ctx, who, kind, W, H, cams, first_frame, n_frames));
+    RT_TRY(check_hit_buffers(ctx, who, d_out));
+    Device& d = ctx->dev[0];
+    DeviceGuard guard(d.id);
+    return hits_launch(ctx, d, (hipStream_t)hip_stream, kind, W, H, cams, first_frame, n_frames,
+                       HitOut{d_out->depth, d_out->object, (float*)d_out->position, (float*)d_out->normal});
+}
+
+// The host calls: chunks of as many frames as keep the context's buffer (the requested channels, one after the
+// other) at or below 256 MiB, at least one; a chunk is traced, copied out and waited for before the next.
+int hits_host(rt_ctx* ctx, const char* who, int kind, int W, int H, const rt_camera* cams, int first_frame, int n_frames,
+              const rt_hit_buffers* out) {
+    RT_TRY(check_hits(ctx, who, kind, W, H, cams, first_frame, n_frames));
+    RT_TRY(check_hit_buffers(ctx, who, out));
+    Device& d = ctx->dev[0];
+    DeviceGuard guard(d.id);
+    const size_t px = (size_t)W * (size_t)H;
+    const size_t sz[4] = {out->depth ? sizeof(float) : 0, out->object ? sizeof(int32_t) : 0,
+                          out->position ? sizeof(rt_vec3) : 0, out->normal ? sizeof(rt_vec3) : 0};
+    char* const host[4] = {(char*)out->depth, (char*)out->object, (char*)out->position, (char*)out->normal};
+    const size_t frame_bytes = px * (sz[0] + sz[1] + sz[2] + sz[3]);
+    const int chunk = (int)std::min<size_t>((size_t)n_frames, std::max<size_t>(1, ((size_t)256 << 20) / frame_bytes));
+    RT_TRY(grow(ctx, &d.d_hits, &d.hits_cap, (size_t)chunk * frame_bytes));
+    char* dev[4];
+    size_t off = 0;
+    for (int c = 0; c < 4; ++c) {
+        dev[c] = sz[c] ? (char*)d.d_hits + off : nullptr;
+        off += (size_t)chunk * px * sz[c];
+    }
+    const HitOut o{(float*)dev[0], (int32_t*)dev[1], (float*)dev[2], (float*)dev[3]};
+    int rc = RT_OK;
+    for (int f0 = 0; f0 < n_frames && rc == RT_OK; f0 += chunk) {
+        const int nf = std::min(chunk, n_frames - f0);
+        rc = hits_launch(ctx, d, d.stream, kind, W, H, cams ? cams + f0 : nullptr, first_frame + f0, nf, o);
+        for (int c = 0; c < 4 && rc == RT_OK; ++c)
+            if (sz[c] && hipMemcpyAsync(host[c] + (size_t)f0 * px * sz[c], dev[c], (size_t)nf * px * sz[c], hipMemcpyDeviceToHost,
+                                        d.stream) != hipSuccess)
+                rc = fail(ctx, RT_ERR_HIP, "%s: hipMemcpyAsync failed", who);
+        // (whatever happened, no copy into the caller's memory is pending when the call returns)
+        const hipError_t e = hipStreamSynchronize(d.stream);
+        if (rc == RT_OK && e != hipSuccess) rc = fail(ctx, RT_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    return rc;
+}
+}  // namespace
+
+int rt_render_hits_device(rt_ctx* ctx, int width, int height, const rt_hit_buffers* d_out, void* hip_stream) {
+    return hits_device(ctx, "rt_render_hits_device", HITS_CTX, width, height, nullptr, 0, 1, d_out, hip_stream);
+}
+int rt_render_path_hits_device(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames,
+                               const rt_hit_buffers* d_out, void* hip_stream) {
+    return hits_device(ctx, "rt_render_path_hits_device", HITS_PATH, width, height, cameras, 0, n_frames, d_out, hip_stream);
+}
+int rt_render_anim_hits_device(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame, int n_frames,
+                               const rt_hit_buffers* d_out, void* hip_stream) {
+    return hits_device(ctx, "rt_render_anim_hits_device", HITS_ANIM, width, height, cameras, first_frame, n_frames, d_out, hip_stream);
+}
+int rt_render_hits(rt_ctx* ctx, int width, int height, const rt_hit_buffers* out) {
+    return hits_host(ctx, "rt_render_hits", HITS_CTX, width, height, nullptr, 0, 1, out);
+}
+int rt_render_path_hits(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int n_frames, const rt_hit_buffers* out) {
+    return hits_host(ctx, "rt_render_path_hits", HITS_PATH, width, height, cameras, 0, n_frames, out);
+}
+int rt_render_anim_hits(rt_ctx* ctx, int width, int height, const rt_camera* cameras, int first_frame, int n_frames,
+                        const rt_hit_buffers* out) {
+    return hits_host(ctx, "rt_render_anim_hits", HITS_ANIM, width, height, cameras, first_frame, n_frames, out);
+}
+
+// One wave and one 32-byte copy: the pixel's view-plane coordinates are the view tables' entries (rt_view.h
+// view_table_value), computed here, so no table is built or read.
+int rt_pick(rt_ctx* ctx, int width, int height, int x, int y, rt_pick_result* out) {
+    RT_TRY(check_hits(ctx, "rt_pick", HITS_CTX, width, height, nullptr, 0, 1));
+    if (!out || x < 0 || x >= width || y < 0 || y >= height)
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_pick: NULL result, or pixel (%d, %d) outside the %dx%d frame", x, y, width, height);
+    const int VH = ctx->view_height > 0 ? ctx->view_height : height;
+    if (height > VH) return fail(ctx, RT_ERR_INVALID_ARG, "frame height %d above the view height %d", height, ctx->view_height);
+    static_assert(sizeof(rt_pick_result) == sizeof(DevPick), "rt_pick_result layout");
+    Device& d = ctx->dev[0];
+    DeviceGuard guard(d.id);
+    LaunchParams lp;
+    std::memset(&lp, 0, sizeof lp);
+    RT_TRY(view_fill(ctx, ctx->cam, width, VH, lp));
+    scene_params(ctx, d, lp);
+    lp.counters = nullptr;
+    if (!d.d_pick) HIP_TRY(ctx, hipMalloc((void**)&d.d_pick, sizeof(DevPick)));
+    const int e = launch_pick(lp, x, y, view_table_value(x, width, lp.pw), view_table_value(y, VH, lp.ph), d.d_pick, d.stream);
+    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "rt_pick launch: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(ctx, hipMemcpyAsync(out, d.d_pick, sizeof(DevPick), hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(d.stream));
+    return RT_OK;
 }
 
 // Double-buffered Tick() on one in-order stream per worker.  Frame k's band set is traced into device

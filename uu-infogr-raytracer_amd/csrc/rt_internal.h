@@ -531,7 +531,29 @@ struct DevSegment {
     int kind, pixel;
 };
 
+// Hit buffers (rt_render_hits*, include/raytracer_hip.h rt_hit_buffers): the four channels of a hit launch in device
+// memory, frame z of the grid at element z * W * H of each; a null channel is not written.  position and normal as
+// three floats per pixel (rt_vec3).  A picked pixel's record (rt_pick): the layout of rt_pick_result.
+struct HitOut {
+    float* depth;
+    int32_t* object;
+    float* position;
+    float* normal;
+};
+struct DevPick {
+    int32_t object;
+    float depth;
+    float position[3];
+    float normal[3];
+};
+
 // Launchers (rt_kernel.hip).  Return hipError_t as int.
+// The primary-only hit kernel over p's frame (one band: band_rows = local_rows = H), n_frames = grid z: the view of
+// the block (p.views null), of views[z] (a camera path), or of views[z] with the scene image z * scene_stride on (a
+// scene track).  Nothing of p beyond the view, the scene tables and the frame geometry is read.
+int launch_hits(const LaunchParams& p, const HitOut& out, void* stream);
+// Pixel (x, y) of p's own view with the view-plane coordinates (lx, ly) of that column and row, one wave -> *out.
+int launch_pick(const LaunchParams& p, int x, int y, float lx, float ly, DevPick* out, void* stream);
 int launch_debug_segments(const LaunchParams& p, int stride, DevSegment* out, int capacity, unsigned* count,
                           void* stream);
 // generic_pow: some material needs the f64 Math.Pow path (exponent not 0.5, 1 or 2).

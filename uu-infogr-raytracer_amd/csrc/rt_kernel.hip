@@ -2424,6 +2424,74 @@ __global__ __launch_bounds__(256) void debug_segments_kernel(LaunchParams p, int
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Hit buffers (rt_render_hits*, rt_pick): what the primary ray of a pixel selects, by TracePixel's rule (:973-993)
+// as level 0 of the trace kernels applies it -- and nothing after it: no shading, no shadow ray, no reflection.
+// ---------------------------------------------------------------------------------
+// One pixel's record.  Nothing selected: depth +inf, object -1 (RT_HIT_NONE), the point 100 along the ray (as the
+// debug view's segment end), normal 0.  A selected hit with t - 0.01 <= 0, which the colour frame renders black
+// (:731, :839), is reported like any other.
+struct PixelHit {
+    float depth;
+    int object;
+    f3 pos, nrm;
+};
+// The primary ray of view-plane coordinates (lx, ly) (:963-971) and its selected hit: nearest_direct's, with the wave's
+// screen-box candidates `pmask` when the view has primary constants.  skip (wave-uniform; a sky wave, sky_tile):
+// nothing can be selected and nothing is tested.  Divergent call, as trace_tile_direct's level 0.
+template <int PATH>
+__device__ __forceinline__ PixelHit primary_hit(const LaunchParams& p, float lx, float ly, unsigned long long pmask, bool skip) {
+    constexpr int rec = 0;  // (the views and scene images of a hit launch go by blockIdx.z alone)
+    const ViewOf<PATH> vw{p, rec};
+    const f3 cam = vw.cam();
+    const f3 vp = add(add(add(cam, scale(vw.right(), lx)), scale(vw.up(), ly)), scale(vw.fwd(), 1.0f * p.nearc));
+    const f3 d = normalize(sub(vp, cam));
+    Tally<false> tl;
+    Hit h{0.0f, HIT_NONE};
+    if (!skip) h = nearest_direct<true, false, PATH>(p, cam, d, tl, pmask, rec);
+    if (h.prim == HIT_NONE) return PixelHit{__builtin_inff(), -1, add(cam, scale(d, 100.0f)), mk(0.0f, 0.0f, 0.0f)};
+    const f3 hp = add(cam, scale(d, h.t));  // :846 / :736
+    if (h.prim >= 0) {
+        const DevSphere s = SceneOf<PATH>::sph(p, rec)[h.prim];  // (the winner's centre: a per-lane fetch)
+        return PixelHit{h.t, h.prim, hp, normalize(sub(hp, mk(s.cx, s.cy, s.cz)))};  // :706
+    }
+    const DevPlane& q = SceneOf<PATH>::pl(p, rec)[~h.prim];
+    return PixelHit{h.t, p.S + ~h.prim, hp, mk(q.nx, q.ny, q.nz)};  // :653: the normal as given
+}
+
+// One wave per 8x8 tile, frames in grid z, each lane its own pixel: a tile row is 32 contiguous bytes of depth or
+// object and 96 of position or normal.  The candidates and the sky test are trace_tile_direct's; a sky wave stores the
+// nothing-selected records without a test.  No LDS, no scratch, no atomics; lanes outside the frame store nothing.
+template <int PATH>
+__global__ __launch_bounds__(WG_THREADS) void hits_kernel(LaunchParams p, HitOut out) {
+    const int lane = threadIdx.x & 63;
+    const TilePixel t = tile_pixel(p, (int)blockIdx.x * TILE_W + (lane & 7), (int)blockIdx.y * TILE_H + (lane >> 3));
+    const unsigned long long pmask = ViewOf<PATH>{p, 0}.prim_const() ? prim_box_mask<PATH>(p, t.x, t.y, 0) : 0;
+    const bool sky = sky_tile<PATH>(p, t, pmask, 0);  // wave-uniform
+    if (!t.valid) return;
+    const PixelHit h = primary_hit<PATH>(p, t.lx, t.ly, pmask, sky);
+    const size_t i = (size_t)blockIdx.z * ((size_t)p.W * (size_t)p.H) + (size_t)t.y * (size_t)p.W + (size_t)t.x;
+    if (out.depth) out.depth[i] = h.depth;  // (kernel arguments: wave-uniform tests)
+    if (out.object) out.object[i] = h.object;
+    if (out.position) {
+        float* q = out.position + 3 * i;
+        q[0] = h.pos.x, q[1] = h.pos.y, q[2] = h.pos.z;
+    }
+    if (out.normal) {
+        float* q = out.normal + 3 * i;
+        q[0] = h.nrm.x, q[1] = h.nrm.y, q[2] = h.nrm.z;
+    }
+}
+
+// rt_pick: one wave, every lane on pixel (x, y) -- so the candidates are the spheres whose box holds the pixel --
+// through the same primary_hit; lane 0 stores the record.
+__global__ __launch_bounds__(WG_THREADS) void pick_kernel(LaunchParams p, int x, int y, float lx, float ly, DevPick* out) {
+    const unsigned long long pmask = p.prim_const ? prim_box_mask<VIEW_ARGS>(p, x, y, 0) : 0;
+    const PixelHit h = primary_hit<VIEW_ARGS>(p, lx, ly, pmask, false);
+    if ((threadIdx.x & 63) == 0)
+        *out = DevPick{h.object, h.depth, {h.pos.x, h.pos.y, h.pos.z}, {h.nrm.x, h.nrm.y, h.nrm.z}};
+}
+
 // Reassemble packed row bands (rt_render_bands layout) into a row-major frame.
 __global__ __launch_bounds__(256) void scatter_bands_kernel(const int32_t* __restrict__ bands,
                                                             int32_t* __restrict__ frame, int W, int H, int band_rows,
@@ -2567,6 +2635,21 @@ int launch_debug_segments(const LaunchParams& p, int stride, DevSegment* out, in
     if (n <= 0) return (int)hipSuccess;
     hipLaunchKernelGGL(debug_segments_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p,
                        stride, out, capacity, count);
+    return (int)hipGetLastError();
+}
+
+int launch_hits(const LaunchParams& p, const HitOut& out, void* stream) {
+    if (p.W <= 0 || p.H <= 0) return (int)hipSuccess;
+    const dim3 grid((unsigned)((p.W + TILE_W - 1) / TILE_W), (unsigned)((p.H + TILE_H - 1) / TILE_H),
+                    (unsigned)(p.n_frames > 1 ? p.n_frames : 1)), block(WG_THREADS);
+    if (p.views == nullptr) hipLaunchKernelGGL(hits_kernel<VIEW_ARGS>, grid, block, 0, (hipStream_t)stream, p, out);
+    else if (p.scene_stride == 0) hipLaunchKernelGGL(hits_kernel<VIEW_PATH>, grid, block, 0, (hipStream_t)stream, p, out);
+    else hipLaunchKernelGGL(hits_kernel<VIEW_ANIM>, grid, block, 0, (hipStream_t)stream, p, out);
+    return (int)hipGetLastError();
+}
+
+int launch_pick(const LaunchParams& p, int x, int y, float lx, float ly, DevPick* out, void* stream) {
+    hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(WG_THREADS), 0, (hipStream_t)stream, p, x, y, lx, ly, out);
     return (int)hipGetLastError();
 }
 

@@ -316,15 +316,14 @@ inline void view_record(const LaunchParams& lp, DevView& v) {
 // same binary32 operations as the kernel would (-ffp-contract=off, correctly rounded
 // division): lx[x] = ((float)x / W - 0.5f) * pw, ly[y] = ((float)y / H - 0.5f) * ph.
 // out: lx[0..W) then ly[0..VH).
+// (one entry: column or row i of n across a view plane `plane` wide or high -- rt_pick's pixel needs no table)
+inline float view_table_value(int i, int n, float plane) {
+    const float p = (float)i / (float)n - 0.5f;
+    return p * plane;
+}
 inline void view_table_values(int W, int VH, float pw, float ph, float* out) {
-    for (int x = 0; x < W; ++x) {
-        const float px = (float)x / (float)W - 0.5f;
-        out[(size_t)x] = px * pw;
-    }
-    for (int y = 0; y < VH; ++y) {
-        const float py = (float)y / (float)VH - 0.5f;
-        out[(size_t)W + (size_t)y] = py * ph;
-    }
+    for (int x = 0; x < W; ++x) out[(size_t)x] = view_table_value(x, W, pw);
+    for (int y = 0; y < VH; ++y) out[(size_t)W + (size_t)y] = view_table_value(y, VH, ph);
 }
 
 // The measured tile order: tiles 0..n-1 (row-major, tx per row) by decreasing cost, ties in natural order, as

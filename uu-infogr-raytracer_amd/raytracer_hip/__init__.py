@@ -467,6 +467,79 @@ class Context:
                                                capacity, C.byref(n)))
         return out[:min(n.value, capacity)], n.value
 
+    # -- hit buffers and picking: what the primary ray of a pixel selects -----------------
+    HIT_CHANNELS = ("depth", "object", "position", "normal")
+    _HIT_DTYPES = {"depth": (np.float32, ()), "object": (np.int32, ()), "position": (np.float32, (3,)),
+                   "normal": (np.float32, (3,))}
+
+    def _hit_arrays(self, n, width, height, channels):
+        unknown = [c for c in channels if c not in self._HIT_DTYPES]
+        if unknown:
+            raise ValueError(f"unknown hit channels {unknown}: one of {self.HIT_CHANNELS}")
+        out = {c: np.empty((n, height, width) + self._HIT_DTYPES[c][1], dtype=self._HIT_DTYPES[c][0]) for c in channels}
+        bufs = abi.rt_hit_buffers(**{c: out[c].ctypes.data for c in out})
+        return out, bufs
+
+    @staticmethod
+    def _hit_pointers(depth, object, position, normal):
+        return abi.rt_hit_buffers(depth or None, object or None, position or None, normal or None)
+
+    def render_hits(self, width: int, height: int, channels=HIT_CHANNELS) -> dict:
+        """The hit buffers of the context's camera and scene (rt_render_hits; synchronous): a dict of the requested
+        channels -- depth float32[H, W] (+inf: nothing), object int32[H, W] (sphere i -> i, plane j -> n_spheres + j,
+        abi.RT_HIT_NONE), position and normal float32[H, W, 3].  Supersampling, adaptive and progressive settings play
+        no part, and stats() does not change."""
+        out, bufs = self._hit_arrays(1, width, height, channels)
+        self._check(self.lib.rt_render_hits(self.ptr, width, height, C.byref(bufs)))
+        return {c: a[0] for c, a in out.items()}
+
+    def render_path_hits(self, cameras, width: int, height: int, channels=HIT_CHANNELS) -> dict:
+        """render_hits for every camera of a path, one launch: arrays with a leading frame axis (rt_render_path_hits)."""
+        cams = path.as_array(cameras)
+        out, bufs = self._hit_arrays(len(cams), width, height, channels)
+        self._check(self.lib.rt_render_path_hits(self.ptr, width, height, cams, len(cams), C.byref(bufs)))
+        return out
+
+    def render_anim_hits(self, cameras=None, width: int = 0, height: int = 0, first_frame: int = 0, n_frames: int = 0,
+                         channels=HIT_CHANNELS) -> dict:
+        """render_hits over the scene track, one launch: frame j = track frame first_frame + j seen from cameras[j]
+        (None: the scenes' own cameras -- n_frames of them, 0: to the track's end), arrays with a leading frame axis
+        (rt_render_anim_hits)."""
+        cams = self._anim_cameras(cameras, first_frame, n_frames or None)
+        out, bufs = self._hit_arrays(len(cams), width, height, channels)
+        self._check(self.lib.rt_render_anim_hits(self.ptr, width, height, cams, first_frame, len(cams), C.byref(bufs)))
+        return out
+
+    def render_hits_device(self, width: int, height: int, depth: int = 0, object: int = 0, position: int = 0,
+                           normal: int = 0, stream: int = 0):
+        """rt_render_hits_device: the channels into device memory at these pointers (0: not written), asynchronous."""
+        bufs = self._hit_pointers(depth, object, position, normal)
+        self._check(self.lib.rt_render_hits_device(self.ptr, width, height, C.byref(bufs), C.c_void_p(stream)))
+
+    def render_path_hits_device(self, width: int, height: int, cameras, depth: int = 0, object: int = 0,
+                                position: int = 0, normal: int = 0, stream: int = 0):
+        """rt_render_path_hits_device: frame f, seen from cameras[f], at element f * width * height of each channel."""
+        cams = path.as_array(cameras)
+        bufs = self._hit_pointers(depth, object, position, normal)
+        self._check(self.lib.rt_render_path_hits_device(self.ptr, width, height, cams, len(cams), C.byref(bufs),
+                                                        C.c_void_p(stream)))
+
+    def render_anim_hits_device(self, width: int, height: int, cameras, depth: int = 0, object: int = 0,
+                                position: int = 0, normal: int = 0, stream: int = 0, first_frame: int = 0):
+        """rt_render_anim_hits_device: frame j = track frame first_frame + j seen from cameras[j] (None: the scenes' own
+        cameras, to the track's end)."""
+        cams = self._anim_cameras(cameras, first_frame, None)
+        bufs = self._hit_pointers(depth, object, position, normal)
+        self._check(self.lib.rt_render_anim_hits_device(self.ptr, width, height, cams, first_frame, len(cams),
+                                                        C.byref(bufs), C.c_void_p(stream)))
+
+    def pick(self, width: int, height: int, x: int, y: int) -> dict:
+        """rt_pick: what pixel (x, y) of the context camera's width x height frame sees -- {"object", "depth",
+        "position", "normal"}, the values render_hits holds there, from a one-wave launch."""
+        r = abi.rt_pick_result()
+        self._check(self.lib.rt_pick(self.ptr, width, height, int(x), int(y), C.byref(r)))
+        return {"object": r.object, "depth": r.depth, "position": r.position.tuple(), "normal": r.normal.tuple()}
+
     def register_host(self, arr: np.ndarray):
         self._check(self.lib.rt_register_host(self.ptr, C.c_void_p(arr.ctypes.data), arr.nbytes))
 
@@ -552,6 +625,11 @@ class RayTracer:
     def OnMouseMove(self, delta_x: float, delta_y: float):
         """RayTracer.OnMouseMove, RayTracer.cs:1058-1061."""
         check(self._ctx.lib, self._ctx.lib.rt_camera_on_mouse_move(C.byref(self._camera), delta_x, delta_y))
+
+    def pick(self, x: int, y: int) -> dict:
+        """What the screen's pixel (x, y) sees from the current camera (Context.pick): the object under a click."""
+        self._ctx.set_camera(self._camera)
+        return self._ctx.pick(self.screen.width, self.screen.height, x, y)
 
     @property
     def camera(self) -> abi.rt_camera:

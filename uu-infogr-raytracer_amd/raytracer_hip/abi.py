@@ -23,6 +23,7 @@ RT_MAX_PATH_FRAMES = 65535  # rt_render_path_bands / rt_render_path: frames per 
 RT_MAX_TRACK_BYTES = 1 << 30  # rt_set_scene_track: the scene images of a track
 RT_MAX_SHUTTER = 256  # rt_render_shutter_bands / rt_render_shutter: sub-frame cameras per output frame
 RT_BANDS_INT32, RT_BANDS_RGB24, RT_BANDS_FRAME = 0, 1, 2
+RT_HIT_NONE = -1  # rt_hit_buffers.object / rt_pick_result.object: the primary ray selects nothing
 RT_OK = 0
 RT_ERR_INVALID_ARG = -1
 RT_ERR_NO_DEVICE = -2
@@ -73,6 +74,15 @@ class rt_view(C.Structure):
 
 class rt_segment(C.Structure):
     _fields_ = [("origin", rt_vec3), ("end", rt_vec3), ("kind", C.c_int32), ("pixel", C.c_int32)]
+
+
+class rt_hit_buffers(C.Structure):
+    """The channels of a hit call, [n_frames][height][width] each; a NULL channel is not written."""
+    _fields_ = [("depth", C.c_void_p), ("object", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p)]
+
+
+class rt_pick_result(C.Structure):
+    _fields_ = [("object", C.c_int32), ("depth", C.c_float), ("position", rt_vec3), ("normal", rt_vec3)]
 
 
 class rt_stats(C.Structure):
@@ -186,6 +196,17 @@ EXPORTS = [
     ("rt_wait", C.c_int, [C.c_void_p]),
     ("rt_write_ppm", C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     ("rt_debug_segments", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    ("rt_render_hits_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_hit_buffers), C.c_void_p]),
+    ("rt_render_path_hits_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int,
+                                             C.POINTER(rt_hit_buffers), C.c_void_p]),
+    ("rt_render_anim_hits_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int,
+                                             C.POINTER(rt_hit_buffers), C.c_void_p]),
+    ("rt_render_hits", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_hit_buffers)]),
+    ("rt_render_path_hits", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int,
+                                      C.POINTER(rt_hit_buffers)]),
+    ("rt_render_anim_hits", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(rt_camera), C.c_int, C.c_int,
+                                      C.POINTER(rt_hit_buffers)]),
+    ("rt_pick", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(rt_pick_result)]),
     ("rt_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("rt_dispatch_order", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("rt_get_stats", C.c_int, [C.c_void_p, C.POINTER(rt_stats)]),
